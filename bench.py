@@ -24,7 +24,11 @@ this process has touched a GPU) unless it already runs under torch.distributed.r
 in which case WORLD_SIZE must equal --gpus.  A rank that cannot join, or an RCCL failure, makes the whole
 run exit non-zero.
 
-Prints ONE JSON line on rank 0 (contract in the build prompt) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and nothing else: inputs, plan, --warmup steps,
+exactly --steps timed steps, the line (`value`, `ms_per_step`, ...).  --full adds every secondary measurement and check:
+CPU baseline, rocprofv3 counter passes, the cached-tables region, the per-kernel HIP-event pass (`roofline`), parity,
+only_flux, host-to-host, retention, BASELINE's other configs and the N-rank check (--no-cpu-baseline, --no-extras and
+--no-live-traffic drop parts of it).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -800,6 +804,28 @@ def end_to_end(device, cfg=None, window=2048):
                     "library's large-block pool (pydisort_amd.pooled(): off by default); best of 3 calls (every call's time listed)"}
 
 
+DUMP_COLUMNS = 2048          # columns in the --dump-outputs sample: 2 048 x 22 KB = 45 MB of float64 for cfg4
+DUMP_LIMIT_BYTES = 64 << 20  # all files of one dump together
+DUMP_SEED = 2024
+
+
+def dump_sample(C, bytes_per_column):
+    """Column indices of the --dump-outputs sample: all C columns when they fit, else a fixed, seeded sample (sorted)."""
+    k = min(C, DUMP_COLUMNS, DUMP_LIMIT_BYTES // bytes_per_column)
+    return np.arange(C) if k == C else np.sort(np.random.default_rng(DUMP_SEED).choice(C, size=k, replace=False))
+
+
+def dump_outputs(plan, directory):
+    """--dump-outputs: what the last timed step computed, as a caller of the timed path receives it (plan.run, then plan.fetch):
+    u [C, 32, 21, 3], u0 [C, 32, 21], flux_up, flux_down_diffuse, flux_down_direct [C, 21], float64, one DIR/<name>.npy each,
+    rows = the columns of dump_sample (the same in every file and every run with the same arguments)."""
+    res = plan.fetch()
+    idx = dump_sample(next(iter(res.values())).shape[0], sum(v[0].nbytes for v in res.values()))
+    os.makedirs(directory, exist_ok=True)
+    for name, v in res.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(v[idx], dtype=np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # rank layout
 # ---------------------------------------------------------------------------------------------------------
@@ -1028,10 +1054,10 @@ def run_rank(a, rank, world, local):
         time.sleep(3600)
     cpu = None
     filled = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not stub:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not stub:
         cpu = cpu_baseline_subprocess()
     live = None
-    if rank == 0 and world == 1 and not a.no_extras and not a.no_live_traffic and not stub:
+    if rank == 0 and world == 1 and a.full and not a.no_extras and not a.no_live_traffic and not stub:
         live = live_traffic(a.columns)  # before this process touches the GPU (the profiler runs a child of its own)
         filled = filled_counters() if live else None
 
@@ -1212,8 +1238,16 @@ def run_rank(a, rank, world, local):
     timed(a.warmup, gather, True, "warm-up steps") if a.warmup > 0 else barrier()
     elapsed = timed(a.steps, gather, True, "timed region")          # THE timed region: exactly --steps steps, fresh inputs every step
     mine["ms_per_step_own"] = 1e3 * own["seconds"] / a.steps
-    elapsed_cached = timed(a.steps, gather, False, "timed region (cached tables)")  # the same on repeated inputs (tables kept from run to run)
-    mine["ms_per_step_own_cached_tables"] = 1e3 * own["seconds"] / a.steps
+    if a.dump_outputs and rank == 0:
+        phase("dump outputs")
+        if plan is not None:
+            dump_outputs(plan, a.dump_outputs)
+        else:
+            print("[bench] --dump-outputs: no plan in this run (RTD_BENCH_STUB): nothing written", file=sys.stderr)
+    elapsed_cached = None
+    if a.full:
+        elapsed_cached = timed(a.steps, gather, False, "timed region (cached tables)")  # the same on repeated inputs (tables kept from run to run)
+        mine["ms_per_step_own_cached_tables"] = 1e3 * own["seconds"] / a.steps
     joined = world
     if ctl is not None:
         total_cols = int(ctl.allreduce(int(C), "sum"))
@@ -1262,16 +1296,17 @@ def run_rank(a, rank, world, local):
     per_rank = ctl.gather(mine) if ctl is not None else [mine]
     phase("HIP-event pass, extras")
     if plan is not None and rank == 0:
-        plan.enable_timing(True)
-        plan.timing(reset=True)
-        for _ in range(max(2, min(a.steps, 5))):
-            plan.run()
-        stage = plan.timing(reset=True)
-        plan.enable_timing(False)
+        if a.full:
+            plan.enable_timing(True)
+            plan.timing(reset=True)
+            for _ in range(max(2, min(a.steps, 5))):
+                plan.run()
+            stage = plan.timing(reset=True)
+            plan.enable_timing(False)
         sweeps = plan.max_sweeps()
 
     extras = {}
-    if rank == 0 and world == 1 and not a.no_extras and not stub:
+    if rank == 0 and world == 1 and a.full and not a.no_extras and not stub:
         plan.close()  # the extras build their own plans: give the arena back first
         plan = None
         extras = extra_measurements(dev, cfg if strong else None, a.columns, live, filled)
@@ -1285,9 +1320,6 @@ def run_rank(a, rank, world, local):
             "value_means": "fresh inputs every step: inputs resident in HBM, nothing kept from step to step -- the per-column "
                            "Legendre tables at -mu0 and the beam attenuations are recomputed like everything else (the reference "
                            "computes them in every call)",
-            "value_cached_tables": total_cols * a.steps / elapsed_cached,
-            "value_cached_tables_means": "the same steps on REPEATED inputs: a plan keeps those per-column tables while its inputs are "
-                                         "unchanged (rtd_tables_mu0_kernel runs once; a serving optimisation, not the headline)",
             "data": "synthetic",
             "config": {"workload": "cfg4: synthetic Henyey-Greenstein, 20 layers, 32 streams, 32 Fourier modes, "
                                    "delta-M on, beam source, u at 21 interfaces x 3 azimuths + fluxes",
@@ -1298,6 +1330,10 @@ def run_rank(a, rank, world, local):
                        "parallelism": f"column-sharded x{world}", "collective": collective,
                        "max_jacobi_sweeps": sweeps},
         }
+        if elapsed_cached is not None:
+            out["value_cached_tables"] = total_cols * a.steps / elapsed_cached
+            out["value_cached_tables_means"] = ("the same steps on REPEATED inputs: a plan keeps those per-column tables while its inputs "
+                                                "are unchanged (rtd_tables_mu0_kernel runs once; a serving optimisation, not the headline)")
         if verified is not None:
             out["config"].update(gather_verified=verified["gather_verified"], ranks_verified=verified["ranks_verified"])
             out["gather_verification"] = verified
@@ -1373,7 +1409,7 @@ def run_rank(a, rank, world, local):
                                               "torch.distributed.run command line end to end, every gathered slot verified bit for bit; evidence "
                                               "profiles/r06_bench_stub_8ranks.json (transport = stub, not_a_rate = true: never a throughput)",
                 "over_rccl": "one-rank communicator on every box (tests/test_gpu_distributed.py); two-rank tests where two GPUs are visible"}
-            if not a.no_extras and not stub:
+            if a.full and not a.no_extras and not stub:
                 out["multi_gpu"]["n_rank_check"] = n_rank_check()
         out.update(extras)
         sys.stdout.flush()
@@ -1399,12 +1435,19 @@ def main():
     ap.add_argument("--gather", choices=("auto", "all", "root", "none"), default="auto",
                     help="N > 1: results of a step to every rank (ncclAllGather), to rank 0 only (ncclSend/ncclRecv), or nowhere; "
                          "auto (default): all-gather unless trial regions show it >= 10 %% slower than root-only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement and check: CPU baseline, rocprofv3 counter passes, cached-tables region, "
+                         "per-kernel HIP-event pass (roofline), parity, only_flux, host-to-host, retention, other configs, N-rank check "
+                         "(default: the headline steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write u, u0 and the fluxes of the last timed step (float64; a fixed, seeded sample of "
+                         f"{DUMP_COLUMNS} columns when the batch is larger) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the parity, only_flux and end-to-end legs (profiling runs: every kernel launch is then the workload)")
+                    help="with --full: skip the parity, only_flux and end-to-end legs (profiling runs: every kernel launch is then the workload)")
     ap.add_argument("--force-dist", action="store_true", help="exercise the multi-rank code path even with one rank")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="take roofline.traffic from the committed PMC passes instead of two rocprofv3 passes of a child run (~20 s)")
+                    help="with --full: take roofline.traffic from the committed PMC passes instead of rocprofv3 passes of a child run")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-child-filled", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
@@ -1422,6 +1465,8 @@ def main():
         return
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ:
         if a.gpus > 1:

@@ -23,7 +23,7 @@ def _bench(args, **env_over):
 
 @pytest.mark.parametrize("gather,prefix", [("all", "rccl ncclAllGather"), ("root", "rccl ncclSend/ncclRecv"), ("none", "rccl communicator")])
 def test_bench_force_dist_runs_the_rccl_path_with_one_rank(gather, prefix):
-    r = _bench(["--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
+    r = _bench(["--gpus", "1", "--force-dist", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
                 "--total-columns", "6000", "--gather", gather])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -188,7 +188,7 @@ def test_bench_verifies_what_it_gathers_before_it_reports():
     """bench.py --gpus 2: the N > 1 line carries gather_verified / ranks_verified = 2 and the compute-only, all-gather and
     root-only rates of the same run (>= 2 devices); a one-rank --force-dist run carries the same fields on any box."""
     n = 2 if _devices() >= 2 else 1
-    args = ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--total-columns", "3000"]
+    args = ["--gpus", str(n), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--total-columns", "3000"]
     if n == 1:
         args.append("--force-dist")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=_clean_env(), capture_output=True, text=True, timeout=900)

@@ -12,7 +12,7 @@ cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 out=gpurun_out/r05
 mkdir -p $out
 export RTD_NO_PIPELINE=1
-bash tools/profile_pmc.sh r05/cfg4_serial python3 bench.py --no-cpu-baseline --no-extras --no-live-traffic --steps 2 --warmup 1 --total-columns 16384 > $out/cfg4_serial.txt 2>&1 || true
+bash tools/profile_pmc.sh r05/cfg4_serial python3 bench.py --full --no-cpu-baseline --no-extras --no-live-traffic --steps 2 --warmup 1 --total-columns 16384 > $out/cfg4_serial.txt 2>&1 || true
 unset RTD_NO_PIPELINE
 bash tools/profile_pmc.sh r05/cfg5 python3 tools/profile_config.py cfg5 128 0 2 > $out/cfg5.txt 2>&1 || true
 if [ -f pythonic-disort_amd/pydisort_amd/librtd_stamps.so ]; then
@@ -21,5 +21,5 @@ fi
 python tools/single_column_latency.py > $out/single_column_latency.txt 2>&1 || true
 python tools/latency_breakdown.py >> $out/single_column_latency.txt 2>&1 || true
 python tools/many_stream_timing.py 24 > $out/many_streams.txt 2>&1 || true
-python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || true
+python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || true
 tail -2 $out/bench.err

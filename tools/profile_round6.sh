@@ -28,7 +28,7 @@ pmc() {  # pmc <outdir under gpurun_out> <log> <program ...>
   bash tools/profile_pmc.sh $dir "$@" > $log 2>&1 && [ -s gpurun_out/$dir/kernel_stats.csv ] && [ -s gpurun_out/$dir/pmc1.txt ] && [ -s gpurun_out/$dir/pmc2.txt ]
 }
 export RTD_NO_PIPELINE=1
-step cfg4_serial_profile 1 pmc r06/cfg4_serial $out/cfg4_serial.txt python3 bench.py --no-cpu-baseline --no-extras --no-live-traffic --steps 2 --warmup 1 --total-columns 16384
+step cfg4_serial_profile 1 pmc r06/cfg4_serial $out/cfg4_serial.txt python3 bench.py --full --no-cpu-baseline --no-extras --no-live-traffic --steps 2 --warmup 1 --total-columns 16384
 step cfg5_profile 1 pmc r06/cfg5 $out/cfg5.txt python3 tools/profile_config.py cfg5 10000 128 2
 unset RTD_NO_PIPELINE
 if [ -s $out/cfg4_serial/pmc1.txt ]; then
@@ -36,7 +36,7 @@ if [ -s $out/cfg4_serial/pmc1.txt ]; then
   step cfg5_traffic_json 1 python3 tools/pmc_to_json.py $out/pmc_traffic_cfg5.json "rocprofv3 --pmc passes of tools/profile_round6.sh (cfg5, windows of 128 columns one after the other)" --columns-per-launch 128 $out/cfg5/pmc*.txt
 fi
 step single_column_latency 0 bash -c "python tools/single_column_latency.py > $out/single_column_latency.txt 2>&1"
-step bench 1 bash -c "python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err && [ -s $out/bench.json ]"
+step bench 1 bash -c "python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err && [ -s $out/bench.json ]"
 tail -2 $out/bench.err
 cat $out/status.txt
 exit $fail
