@@ -278,9 +278,40 @@ struct RowFmacDpp64 {
 
 // acc += (lane K of the caller's own 16-lane DPP row of `src`) * mul: one v_fmac_f64_dpp row_newbcast.  `src` comes from an LDS
 // load (no VALU write in front of the DPP read: no hazard for tools/check_dpp_hazards.py to find).
-template <int K>
+template <int K, bool NEG = false>
 __device__ __forceinline__ void fmac_bcast(double& acc, const double src, const double mul) {
-  asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mul), "n"(K));
+  if constexpr (NEG)  // acc -= ... (the sign as an operand modifier: no negated copy of mul)
+    asm("v_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mul), "n"(K));
+  else
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mul), "n"(K));
+}
+
+// sum_k (src of lane k of the caller's 16-lane DPP row) * m[k]: sixteen v_fmac_f64_dpp row_newbcast in ONE asm statement.  src is a
+// compiler-visible VALU result whose DPP reads the compiler's hazard recogniser does not see: the s_nop in front gives the two wait
+// states they need, and no move of src that the compiler might insert can land between them.
+__device__ __forceinline__ double dot_bcast16(const double src, const double (&m)[16]) {
+  double acc = 0.0;
+  asm("s_nop 1\n\t"
+      "v_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %3 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %5 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %7 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %8 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %9 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %10 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %11 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %12 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %13 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %14 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %15 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %16 row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %1, %17 row_newbcast:15 row_mask:0xf bank_mask:0xf"
+      : "+v"(acc)
+      : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]), "v"(m[6]), "v"(m[7]), "v"(m[8]), "v"(m[9]),
+        "v"(m[10]), "v"(m[11]), "v"(m[12]), "v"(m[13]), "v"(m[14]), "v"(m[15]));
+  return acc;
 }
 
 // ---- NP = 32, round 5: the triangular products of the eigen stage with the rows of L SPREAD OVER THE LANES ----------------
@@ -305,12 +336,12 @@ struct LRowN {  // row r of L: lane t of every DPP row holds L[r][16 g + t] in g
     return x;
   }
 };
-template <int NP, int I, int IEND>
-struct AxpyRowN {  // acc[i] += L[r][i] * mul for i = I .. IEND - 1
+template <int NP, int I, int IEND, bool NEG = false>
+struct AxpyRowN {  // acc[i] += L[r][i] * mul (NEG: -=) for i = I .. IEND - 1
   static __device__ __forceinline__ void run(double (&acc)[NP], const LRowN<NP>& row, const double mul) {
     if constexpr (I < IEND) {
-      fmac_bcast<I % 16>(acc[I], row.g[I / 16], mul);
-      AxpyRowN<NP, I + 1, IEND>::run(acc, row, mul);
+      fmac_bcast<I % 16, NEG>(acc[I], row.g[I / 16], mul);
+      AxpyRowN<NP, I + 1, IEND, NEG>::run(acc, row, mul);
     }
   }
 };
@@ -344,6 +375,20 @@ __device__ __forceinline__ double transpose_reduce_scaled2(const double (&a)[NP]
 #pragma unroll
   for (int i = 0; i < O; ++i) v[i] = level_add<O, true>(fma(b[i], t, a[i] * s), fma(b[i + O], t, a[i + O] * s), hi);
   return transpose_reduce<O>(v, j);
+}
+
+// F = L^T R, column j of R in the lane (q[r] = R[r][j]):  w[i] = sum_{r >= i} L[r][i] q[r], the rows of L spread over the lanes
+// (LRowN): one LDS read per row and lane instead of one broadcast read per FMA (NP = 16: 16 reads instead of 136)
+template <int NP, bool PACKED>
+__device__ __forceinline__ void lt_product(double (&w)[NP], const double* L_, const double (&q)[NP], const int t16) {
+#pragma unroll
+  for (int i = 0; i < NP; ++i) w[i] = 0.0;
+  static_for<0, NP>([&](auto rc) {
+    constexpr int r = decltype(rc)::value;
+    const LRowN<NP> row = LRowN<NP>::template load<r, PACKED>(L_, t16);
+    AxpyRowN<NP, 0, r + 1>::run(w, row, q[r]);
+    if constexpr ((r & 3) == 3) RTD_FENCE();
+  });
 }
 
 // ---- NP = 32: blocked (2 x 2 blocks of 16) in the same one-column-per-lane layout.  A problem is two DPP rows of 16 lanes:
@@ -490,8 +535,8 @@ __device__ __forceinline__ ProbId locate(const RtdDev& d, const int tx = threadI
 // (the lanes write the rotated pair into (X, Y) or into (Y, X): four coefficient selects, no column selects).  Every one
 // of the NP (NP - 1) / 2 pairs meets exactly once per sweep whatever the arrangement the sweep starts from, so sweeps
 // simply follow each other (tools/jacobi_schedule.py replays the schedule and checks this).  The columns wander; each
-// carries the index it started with, and the lanes put them back in that order after the last sweep (the
-// boundary-condition kernel's speculative diagonal pivoting relies on eigen-columns that stay next to their diagonal).
+// carries the index it started with, and the lanes put them back in that order after the last sweep (NP = 16: they are stored
+// under it; the boundary-condition kernel's speculative diagonal pivoting relies on eigen-columns that stay next to their diagonal).
 // ------------------------------------------------------------------------------------------------
 template <int NP>
 struct JSched {  // after the rotation of step s: slots with (p & sw[s]) hand on X instead of Y; the move is slot ^ mk[s]
@@ -731,6 +776,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
   __shared__ double sCoef[NP == 32 ? GPW * TROWS : 1];
   __shared__ double sY0[NP == 32 ? TROWS : 1];
   double w[NP];  // column j of F = L^T R, then of k Z
+  int ecol = 0;  // NP = 16: the index of the eigen-column the lane holds after the sweeps (the columns are not put back in order)
   // beam source terms of this lane's stream, sum_l (omega w_l Y_l[j]) Ybar_l(-mu0) over the even / odd l - m: they fall out of
   // the assembly loop for one FMA per term (the second pass over the moments that stage 2 used to make is gone)
   double xe_sum = 0.0, xo_sum = 0.0;
@@ -853,13 +899,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     for (int i = 0; i < NP; ++i)
         if (!PACKED || j <= i) L_[lix(i, 0) + j] = pcol[i];
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      double a = 0.0;
-#pragma unroll
-      for (int r = i; r < NP; ++r) a += L_[lix(r, i)] * qcol[r];
-      w[i] = a;
-    }
+    lt_product<NP, PACKED>(w, L_, qcol, j & 15);  // F = L^T R
   } else if constexpr (NP == 32) {
     // One parity at a time: Pm is assembled, factorised and parked in LDS before Qm is touched, so that the accumulator
     // and the Cholesky column of only ONE of the two matrices are alive at once (NP = 32: 128 VGPRs less).
@@ -932,17 +972,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     cholesky_columns32(qcol, j, sTab);  // Qm = R R^T
     RTD_ESTAMP(4);
     __syncthreads();
-    {  // F = L^T R with the rows of L spread over the lanes (LRowN)
-      const int t16 = j & 15;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) w[i] = 0.0;
-      static_for<0, NP>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        const LRowN<NP> row = LRowN<NP>::template load<r, PACKED>(L_, t16);
-        AxpyRowN<NP, 0, r + 1>::run(w, row, qcol[r]);
-        if constexpr ((r & 3) == 3) RTD_FENCE();
-      });
-    }
+    lt_product<NP, PACKED>(w, L_, qcol, j & 15);  // F = L^T R
   } else if constexpr (NP == 64) {
     // 66 ... 128 streams: one wavefront per SIMD (512 registers), nothing hides a latency, and only the 256 architectural registers
     // can be VALU operands.  (a) One parity at a time, as at NP = 32: Pm is assembled, factorised and parked in LDS before Qm is
@@ -1032,17 +1062,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     cholesky_columns<NP>(qcol, j);  // Qm = R R^T
     RTD_ESTAMP(4);
     __syncthreads();
-    {  // F = L^T R with the rows of L spread over the lanes (LRowN; round 5: as at NP = 32)
-      const int t16 = j & 15;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) w[i] = 0.0;
-      static_for<0, NP>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        const LRowN<NP> row = LRowN<NP>::template load<r, PACKED>(L_, t16);
-        AxpyRowN<NP, 0, r + 1>::run(w, row, qcol[r]);
-        if constexpr ((r & 3) == 3) RTD_FENCE();
-      });
-    }
+    lt_product<NP, PACKED>(w, L_, qcol, j & 15);  // F = L^T R (round 5: as at NP = 32)
   } else {
   // D+/D- split by parity of (l - m): Ae = 2 sum_even c_l Y_l Y_l^T, Ao likewise (:123-125)
   double acc_e[NP], acc_o[NP];
@@ -1095,12 +1115,16 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     for (int i = 0; i < NP; ++i)
         if (!PACKED || j <= i) L_[lix(i, 0) + j] = pcol[i];
     __syncthreads();
+    if constexpr (NP == 16) {
+      lt_product<NP, PACKED>(w, L_, qcol, j);  // F = L^T R: one DPP row per problem
+    } else {
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      double a = 0.0;
+      for (int i = 0; i < NP; ++i) {
+        double a = 0.0;
 #pragma unroll
-      for (int r = i; r < NP; ++r) a += L_[lix(r, i)] * qcol[r];
-      w[i] = a;
+        for (int r = i; r < NP; ++r) a += L_[lix(r, i)] * qcol[r];
+        w[i] = a;
+      }
     }
   }
   }
@@ -1153,14 +1177,20 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       w[i] = u ? recv : xh[i];
       w[H + i] = u ? yh[i] : recv;
     }
-    // ... and every column returns to the lane it started in (its index j): the source lane of lane j through LDS
-    int* where = reinterpret_cast<int*>(sV[grp][0]);
-    where[u ? iy : ix] = j;
-    __syncthreads();
-    const int src = where[j];
+    if constexpr (NP == 16) {
+      // NP = 16: the column stays where the sweeps left it and stage 2 stores it under the index it carries -- nothing in between
+      // depends on which lane holds which eigen-column (its sums over them are transposed reductions); no 32 ds_bpermute here
+      ecol = u ? iy : ix;
+    } else {
+      // ... and every column returns to the lane it started in (its index j): the source lane of lane j through LDS
+      int* where = reinterpret_cast<int*>(sV[grp][0]);
+      where[u ? iy : ix] = j;
+      __syncthreads();
+      const int src = where[j];
 #pragma unroll
-    for (int i = 0; i < NP; ++i) w[i] = __shfl(w[i], src, NP);
-    __syncthreads();
+      for (int i = 0; i < NP; ++i) w[i] = __shfl(w[i], src, NP);
+      __syncthreads();
+    }
   }
   RTD_ESTAMP(6);
 #ifdef RTD_EIG_STAMPS
@@ -1174,6 +1204,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
   int tx = threadIdx.x;
   asm volatile("" : "+v"(tx));
   const int grp = tx / NP, j = tx % NP;
+  const int je = NP == 16 ? ecol : j;  // the eigen-index of the lane's column: where k, E and the columns of Y and A are stored
   const ProbId id = locate<NP>(d, tx);
   const int P = d.P, m = id.m, c = id.c, l = id.l;
   const bool valid = id.valid;
@@ -1208,7 +1239,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
   // eigenvector blocks (:190-198): V = T^-1 L^-T Z, U = (alpha+beta) V / k = -T^-1 L Z / k; stored as
   // Y = L^-T Z and A = L Z, from which Gp = (Y - A/k)/T, Gm = (Y + A/k)/T, V^-1 = A^T T, U^-1 = -k Y^T T
   double ya[NP];
-  if constexpr (NP >= 32) {  // the rows of L spread over the lanes (LRowN): ya[r] final, then its multiples leave the rows above
+  if constexpr (NP >= 16) {  // the rows of L spread over the lanes (LRowN): ya[r] final, then its multiples leave the rows above
     const int t16 = j & 15;
 #pragma unroll
     for (int i = 0; i < NP; ++i) ya[i] = zc[i];
@@ -1217,7 +1248,8 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       ya[r] *= dinv[r];
       if constexpr (r > 0) {
         const LRowN<NP> row = LRowN<NP>::template load<r, PACKED>(L_, t16);
-        AxpyRowN<NP, 0, r>::run(ya, row, -ya[r]);
+        // (the sign as the FMA's operand modifier; NP = 64 keeps the negated copy: with the modifier it spilled 3 registers more)
+        AxpyRowN<NP, 0, r, NP <= 32>::run(ya, row, NP <= 32 ? ya[r] : -ya[r]);
       }
       if constexpr ((r & 3) == 0) RTD_FENCE();
     });
@@ -1250,10 +1282,10 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     if (valid) {
       double* Ym = d.Ym + base * NP * NP;
 #pragma unroll
-      for (int i = 0; i < NP; ++i) Ym[i * NP + j] = ya[i];
-      d.kk[base * NP + j] = kj;
+      for (int i = 0; i < NP; ++i) Ym[i * NP + je] = ya[i];
+      d.kk[base * NP + je] = kj;
       if constexpr (NP != 32) ekj = exp(-kj * dts);
-      d.Ek[base * NP + j] = ekj;
+      d.Ek[base * NP + je] = ekj;
     }
   };
   // NP = 32: Y leaves behind the beam stage, in one run of stores.  This kernel reloads spilled registers in the beam stage: stored
@@ -1271,58 +1303,86 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     const double fac = I0_c * (0.25 / M_PI) * (id.mg == 0 ? 1.0 : 2.0);
     const double xe = fac * xe_sum, xo = fac * xo_sum;
     const double txd = 2.0 * T_j * xe * invmu_j;  // T (x+ - x-)
-    v0[j] = txd;
-    __syncthreads();
-    // Qm v0 through Qm = L^-T H L^-1 = Y k^2 Y^T (exact for the rotated columns whatever their convergence):
-    // lane e forms k_e^2 (Y^T v0)_e, the sum over the eigen-index is a transposed reduction in registers
-    double qv;
-    {
-      double tq = 0.0;
+    double sh, ps;
+    if constexpr (NP == 16) {
+      // One DPP row per problem: the vectors the lanes share (T (x+ - x-), rhat, g, shat, t) reach their FMAs as row broadcasts
+      // (dot_bcast16) -- no LDS round trips, no barriers -- and t = Z h = L^T (L^-T Z h) = L^T shat comes from the column of L
+      // that g reads, instead of from a second transposed reduction (four levels of selects and lane moves, ~7 VALU per
+      // element pair, against one FMA per element)
+      double x[NP];
+      const double tq = dot_bcast16(txd, ya) * k2;  // lane e: k_e^2 (Y^T v0)_e
 #pragma unroll
-      for (int i = 0; i < NP; ++i) tq += ya[i] * v0[i];
-      tq *= k2;
+      for (int i = 0; i < NP; ++i) x[i] = ya[i] * tq;
+      const double qv = transpose_reduce<NP>(x, j);  // Qm v0 = Y k^2 Y^T v0 (exact for the rotated columns)
+      const double rmu0 = fast_rcp(mu0);
+      const double rhat = 2.0 * T_j * xo * invmu_j * rmu0 - qv;
+      double lc[NP];  // column j of L (zero above the diagonal)
+#pragma unroll
+      for (int r = 0; r < NP; ++r) lc[r] = L_[lix(r, 0) + j];
+      const double g = dot_bcast16(rhat, lc);                          // g = L^T rhat
+      const double h = dot_bcast16(g, zc) * fast_rcp(rmu0 * rmu0 - k2);  // h = Z^T g / (1/mu0^2 - k^2)
+#pragma unroll
+      for (int i = 0; i < NP; ++i) x[i] = ya[i] * h;
+      sh = transpose_reduce<NP>(x, j);     // shat = L^-T Z h = Y h
+      const double e = dot_bcast16(sh, lc);  // t = L^T shat
+      double lr[NP];  // row j of L
+#pragma unroll
+      for (int r = 0; r < NP; ++r) lr[r] = L_[lix(j, 0) + r];
+      ps = dot_bcast16(e, lr);  // Pm shat = L t
+    } else {
+      v0[j] = txd;
+      __syncthreads();
+      // Qm v0 through Qm = L^-T H L^-1 = Y k^2 Y^T (exact for the rotated columns whatever their convergence):
+      // lane e forms k_e^2 (Y^T v0)_e, the sum over the eigen-index is a transposed reduction in registers
+      double qv;
+      {
+        double tq = 0.0;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) tq += ya[i] * v0[i];
+        tq *= k2;
+        if constexpr (NP == 32) {
+          qv = transpose_reduce_scaled<NP>(ya, tq, j);
+        } else {
+          double x[NP];
+#pragma unroll
+          for (int i = 0; i < NP; ++i) x[i] = ya[i] * tq;
+          qv = transpose_reduce<NP>(x, j);
+        }
+      }
+      const double rmu0 = fast_rcp(mu0);
+      const double rhat = 2.0 * T_j * xo * invmu_j * rmu0 - qv;
+      v1[j] = rhat;
+      __syncthreads();
+      double g = 0.0;  // g = L^T rhat
+#pragma unroll
+      for (int r = 0; r < NP; ++r) g += ((!PACKED || r >= j) ? L_[lix(r, 0) + j] : 0.0) * v1[r];  // column j of L (zero above the diagonal)
+      v2[j] = g;
+      __syncthreads();
+      double h = 0.0;  // h = Z^T g / (1/mu0^2 - k^2)
+#pragma unroll
+      for (int i = 0; i < NP; ++i) h += zc[i] * v2[i];
+      h *= fast_rcp(rmu0 * rmu0 - k2);
+      // shat = L^-T Z h = Y h  and  t = L^T shat = Z h  (sums over the eigen-index = lanes): no triangular solve
+      double e;
       if constexpr (NP == 32) {
-        qv = transpose_reduce_scaled<NP>(ya, tq, j);
+        sh = transpose_reduce_scaled<NP>(ya, h, j);
+        e = transpose_reduce_scaled<NP>(zc, h, j);
       } else {
         double x[NP];
 #pragma unroll
-        for (int i = 0; i < NP; ++i) x[i] = ya[i] * tq;
-        qv = transpose_reduce<NP>(x, j);
+        for (int i = 0; i < NP; ++i) x[i] = ya[i] * h;
+        sh = transpose_reduce<NP>(x, j);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) x[i] = zc[i] * h;
+        e = transpose_reduce<NP>(x, j);
       }
+      __syncthreads();
+      v2[j] = e;
+      __syncthreads();
+      ps = 0.0;  // Pm shat = L (L^T shat) = L t
+#pragma unroll
+      for (int r = 0; r < NP; ++r) ps += ((!PACKED || r <= j) ? L_[lix(j, 0) + r] : 0.0) * v2[r];  // row j of L
     }
-    const double rmu0 = fast_rcp(mu0);
-    const double rhat = 2.0 * T_j * xo * invmu_j * rmu0 - qv;
-    v1[j] = rhat;
-    __syncthreads();
-    double g = 0.0;  // g = L^T rhat
-#pragma unroll
-    for (int r = 0; r < NP; ++r) g += ((!PACKED || r >= j) ? L_[lix(r, 0) + j] : 0.0) * v1[r];  // column j of L (zero above the diagonal)
-    v2[j] = g;
-    __syncthreads();
-    double h = 0.0;  // h = Z^T g / (1/mu0^2 - k^2)
-#pragma unroll
-    for (int i = 0; i < NP; ++i) h += zc[i] * v2[i];
-    h *= fast_rcp(rmu0 * rmu0 - k2);
-    // shat = L^-T Z h = Y h  and  t = L^T shat = Z h  (sums over the eigen-index = lanes): no triangular solve
-    double sh, e;
-    if constexpr (NP == 32) {
-      sh = transpose_reduce_scaled<NP>(ya, h, j);
-      e = transpose_reduce_scaled<NP>(zc, h, j);
-    } else {
-      double x[NP];
-#pragma unroll
-      for (int i = 0; i < NP; ++i) x[i] = ya[i] * h;
-      sh = transpose_reduce<NP>(x, j);
-#pragma unroll
-      for (int i = 0; i < NP; ++i) x[i] = zc[i] * h;
-      e = transpose_reduce<NP>(x, j);
-    }
-    __syncthreads();
-    v2[j] = e;
-    __syncthreads();
-    double ps = 0.0;  // Pm shat = L (L^T shat) = L t
-#pragma unroll
-    for (int r = 0; r < NP; ++r) ps += ((!PACKED || r <= j) ? L_[lix(j, 0) + r] : 0.0) * v2[r];  // row j of L
     const double rT = fast_rcp(T_j);
     const double s_j = sh * rT;
     const double d_j = mu0 * (txd - ps) * rT;
@@ -1356,14 +1416,15 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
                       "+v"(aa[9]), "+v"(aa[10]), "+v"(aa[11]), "+v"(aa[12]), "+v"(aa[13]), "+v"(aa[14]), "+v"(aa[15]));
     asm volatile("" : "+v"(aa[16]), "+v"(aa[17]), "+v"(aa[18]), "+v"(aa[19]), "+v"(aa[20]), "+v"(aa[21]), "+v"(aa[22]), "+v"(aa[23]),
                       "+v"(aa[24]), "+v"(aa[25]), "+v"(aa[26]), "+v"(aa[27]), "+v"(aa[28]), "+v"(aa[29]), "+v"(aa[30]), "+v"(aa[31]));
-  } else if constexpr (NP == 64) {  // the same product at 128 streams: four registers per spread row, four accumulation chains
-    const int t16 = j & 15;
+  } else if constexpr (NP == 16 || NP == 64) {  // the same product at 32 and 128 streams: one / four registers per spread row and
+    const int t16 = j & 15;                       // as many accumulation chains
     static_for<0, NP>([&](auto rc) {
       constexpr int r = decltype(rc)::value;
       const LRowN<NP> row = LRowN<NP>::template load<r, PACKED>(L_, t16);
       double a[NP / 16] = {};
       DotRowN<NP, 0, r + 1>::run(a, row, zc);
-      aa[r] = (a[0] + a[1]) + (a[2] + a[3]);
+      if constexpr (NP == 16) aa[r] = a[0];
+      else aa[r] = (a[0] + a[1]) + (a[2] + a[3]);
       if constexpr ((r & 3) == 3) RTD_FENCE();
     });
   } else {
@@ -1379,7 +1440,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
   if (valid) {
     double* Am = d.Am + base * NP * NP;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) Am[i * NP + j] = aa[i];
+    for (int i = 0; i < NP; ++i) Am[i * NP + je] = aa[i];
     if constexpr (NP == 32) {
       if (d.beam) {
         d.Bv[base * 2 * NP + j] = bv_up;
@@ -1413,7 +1474,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
 #pragma unroll
     for (int i = 0; i < NP; ++i) zn += ya_t[i] * (d.T[i] * d.invmu[i]);
     zn *= -0.5 * kj;
-    if (valid && act) d.zneg[((long)c * d.L + l) * NP + j] = zn;
+    if (valid && act) d.zneg[((long)c * d.L + l) * NP + je] = zn;
     const double* sp = d.spoly + ((long)c * d.L + l) * d.Ns;
     const double rk = rk0;
     // v_l at the layer's own boundaries (vb: what every boundary-condition kernel reads -- none evaluates a polynomial).  The
