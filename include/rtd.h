@@ -182,7 +182,14 @@ int rtd_plan_solve(rtd_plan* plan);
  * fluxes [C][ntau]: flux_up, flux_down diffuse, flux_down direct
  * ulast  [C][NQuad][ntau]: last Fourier mode u^{M-1} (for return_Fourier_error), may be NULL
  * antiderivative bit 0 switches every output to the tau-antiderivative (is_antiderivative_wrt_tau);
- * bit 1 evaluates u without the Nakajima-Tanaka corrections even when rtd_plan_set_nt is active.
+ * bit 1 evaluates u without the Nakajima-Tanaka corrections even when rtd_plan_set_nt is active;
+ * bit 2 (value 4) switches every output -- u with its Nakajima-Tanaka corrections, u0, ulast and the three fluxes -- to its
+ * derivative with respect to tau, the caller's UNSCALED optical depth (inside layer l the delta-M scaled depth moves at
+ * d tau* / d tau = scale_tau[l]).  The solution is closed-form per layer, so this is exact and costs what a value costs; the
+ * reference leaves it to the autograd package (pydisort(..., autograd_compatible=True)).  The layer of a point is found as for
+ * the values, argmax(tau <= tau_arr): at an interface tau = tau_arr[l] the result is the one-sided derivative from ABOVE, i.e.
+ * of layer l, which ends there; at tau = 0 it is the right derivative.  Derivatives are generally discontinuous across
+ * interfaces.  d(flux_down_direct)/d tau = -flux_down_direct / mu0.  Bits 0 and 2 together: RTD_ERR_ARG.
  * Any output pointer may be NULL.  Synchronous (returns when the host arrays are filled).
  * Returns RTD_ERR_TAU_RANGE if some tau lies outside its column (the reference raises ValueError). */
 int rtd_plan_evaluate(rtd_plan* plan, int32_t ntau, const double* tau, int32_t nphi, const double* phi,
@@ -201,6 +208,12 @@ int rtd_plan_set_nt(rtd_plan* plan, int32_t nleg_all, const double* weighted_leg
 
 /* Throughput form: evaluation points are uploaded once, results stay in HBM. */
 int rtd_plan_set_eval_points(rtd_plan* plan, int32_t ntau, const double* tau, int32_t nphi, const double* phi);
+/* What rtd_plan_run / rtd_plan_run_fetch evaluate at the stored points (and rtd_plan_fetch then returns): order 0 the values
+ * (default), -1 the tau-antiderivatives (bit 0 of rtd_plan_evaluate's flag word), +1 the tau-derivatives (its bit 2, same
+ * one-sided convention at the interfaces).  A streamed batch too large to retain thus returns derivatives host to host through
+ * the window pipeline.  Any order other than 0 takes the evaluation kernel: the fused interface evaluation is value-only.
+ * RTD_ERR_ARG for any other order. */
+int rtd_plan_set_eval_order(rtd_plan* plan, int32_t order);
 /* solve + evaluate at the stored points, asynchronous on the plan's stream */
 int rtd_plan_run(rtd_plan* plan);
 /* copy the results of the last rtd_plan_run to the host (any pointer may be NULL) */

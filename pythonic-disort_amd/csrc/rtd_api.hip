@@ -311,6 +311,7 @@ struct rtd_plan {
   std::vector<double> ev_img;
   bool quad_pending = false, cols_pending = false, ev_pending = false;
   // evaluation buffers (grown on demand)
+  int eval_order = 0;  // rtd_plan_set_eval_order: -1 antiderivative, 0 value, +1 tau-derivative at the stored points
   bool ev_iface = false;  // the stored evaluation points are [0, tau_arr] of every column (fused evaluation possible)
   double* um_buf = nullptr;  // [Cw][M][L+1][2 NP]: Fourier modes at the interfaces, written by the boundary-condition kernel
   int64_t cap_um = 0;
@@ -560,7 +561,7 @@ int launch_windows(rtd_plan* p, bool with_solve, const RtdEval* ev, bool with_nt
     // run-path points at the layer interfaces: the boundary-condition kernel evaluates the Fourier modes there itself
     // (rtd_plan_evaluate -- the closures -- always takes the evaluation kernel, whatever the window count: a column's
     // closure values must not depend on the batch it was solved in)
-    const bool fused = allow_fused && with_solve && ev && ev->antider == 0 && p->ev_iface && p->um_buf && rtd_bc_fuses_eval(d);
+    const bool fused = allow_fused && with_solve && ev && ev->antider == 0 && ev->deriv == 0 && p->ev_iface && p->um_buf && rtd_bc_fuses_eval(d);
     d.um = fused ? p->um_buf : nullptr;
     if (tm) {
       (void)hipStreamSynchronize(s);
@@ -1328,12 +1329,14 @@ int rtd_plan_set_eval_points(rtd_plan* p, int32_t ntau, const double* tau, int32
   return 0;
 }
 
-static RtdEval make_eval(rtd_plan* p, int antider, bool want_u) {
+// order: -1 the tau-antiderivative, 0 the value, +1 the tau-derivative of every output
+static RtdEval make_eval(rtd_plan* p, int order, bool want_u) {
   RtdEval e{};
   const int64_t C = p->d.C, Qr = 2 * p->d.N;
   e.ntau = p->ev_ntau;
   e.nphi = p->ev_nphi;
-  e.antider = antider;
+  e.antider = order < 0 ? 1 : 0;
+  e.deriv = order > 0 ? 1 : 0;
   e.tau = p->ev_tau;
   e.phi = p->ev_phi;
   e.u = (want_u && p->ev_nphi > 0) ? p->ev_u : nullptr;
@@ -1349,8 +1352,15 @@ int rtd_plan_run(rtd_plan* p) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
   if (!p->have_quad || !p->have_cols || p->ev_ntau < 1) return fail(RTD_ERR_STATE, "inputs or evaluation points missing");
   HIP_TRY(hipSetDevice(p->device));
-  RtdEval e = make_eval(p, 0, true);
+  RtdEval e = make_eval(p, p->eval_order, true);
   return launch_solve(p, true, &e, p->have_nt);
+}
+
+int rtd_plan_set_eval_order(rtd_plan* p, int32_t order) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (order < -1 || order > 1) return fail(RTD_ERR_ARG, "evaluation order must be -1, 0 or +1");
+  p->eval_order = order;
+  return 0;
 }
 
 static int fetch_queued(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir) {
@@ -1420,7 +1430,7 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
       if (fls[f]) { std::memcpy(fls[f] + c0 * nt, src, (size_t)(cnt * nt) * 8); src += cnt * nt * 8; }
     return 0;
   };
-  RtdEval e = make_eval(p, 0, true);
+  RtdEval e = make_eval(p, p->eval_order, true);
   int rc = launch_windows(p, true, &e, p->have_nt, [&](int w, int64_t c0, int cnt) -> int {
     const int k = w & 1;
     if (w >= 2) {  // the slab of window w - 2 must have been drained before it is overwritten
@@ -1459,10 +1469,11 @@ int rtd_plan_evaluate(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi
                       double* ulast) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
   if (!p->solved) return fail(RTD_ERR_STATE, "evaluate before solve");
+  if ((antiderivative & 1) && (antiderivative & 4)) return fail(RTD_ERR_ARG, "antiderivative (bit 0) and derivative (bit 2) exclude each other");
   int rc = rtd_plan_set_eval_points(p, ntau, tau, nphi, phi);
   if (rc) return rc;
   const bool skip_nt = (antiderivative & 2) != 0;
-  RtdEval e = make_eval(p, antiderivative & 1, u != nullptr);
+  RtdEval e = make_eval(p, (antiderivative & 1) ? -1 : (antiderivative & 4) ? 1 : 0, u != nullptr);
   // one window, or a retained plan (rtd_plan_create_retained): what the evaluators need of the solve is resident for every
   // column, only the evaluation kernels run.  Several windows without retention: they are solved again, window by window,
   // with the evaluation behind each (the throughput form rtd_plan_run is the intended entry point for such batches).

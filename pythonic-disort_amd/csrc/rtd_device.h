@@ -90,6 +90,7 @@ struct RtdEval {
   const double* um_in;  // [C][M][ntau][Q2] Fourier modes already formed by the boundary-condition kernel (else null)
   const int* run_if_set;  // not null: the evaluation kernel leaves at once unless this flag is set (see rtd_launch_eval)
   int mchunk;  // Fourier modes per pass of the evaluation kernel (set by rtd_launch_eval; 0: all)
+  int deriv;   // every output is the derivative with respect to the (unscaled) tau; never together with antider
 };
 
 // Nakajima-Tanaka corrections (rtd_nt.hip)

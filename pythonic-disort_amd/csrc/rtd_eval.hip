@@ -4,7 +4,9 @@
 // (src/PythonicDISORT/_assemble_intensity_and_fluxes.py:170-330, :334-433, :446-524, :527-613):
 // layer lookup (:185), delta-M tau mapping (:190-195), non-positive exponents (:197-203),
 // GC exp(K dtau) + B exp(-tau*/mu0) + v(tau*) (:221-254), Fourier sum (:256-260), fluxes (:519, :601),
-// rescale (:262), and their is_antiderivative_wrt_tau variants.  One workgroup per (column, tau point);
+// rescale (:262), and their is_antiderivative_wrt_tau variants, and the tau-derivatives of all of them (no counterpart in the
+// reference, which leaves them to autograd: every term is an exponential or a polynomial in tau*, so the derivative multiplies
+// by the rates the antiderivative divides by, d tau*/d tau = scale_tau inside a layer).  One workgroup per (column, tau point);
 // the M x Q x Q temporary of the reference is never formed: G rows are streamed once per point.
 #include <algorithm>
 
@@ -39,7 +41,9 @@ __device__ __forceinline__ double transpose_reduce(double (&v)[NP], int jj) {
   return v[0];
 }
 
-template <int NP>
+// DERIV: the tau-derivative instance.  A template parameter, not one more runtime flag: the value / antiderivative instance
+// then compiles to the code it was before the derivative existed (registers, scalar spills: HISTORY.md).
+template <int NP, bool DERIV = false>
 __global__ __launch_bounds__(EVAL_THREADS) void rtd_eval_kernel(RtdDev d, RtdEval ev) {
   constexpr int Q = 2 * NP;
   extern __shared__ double smem[];
@@ -71,7 +75,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void rtd_eval_kernel(RtdDev d, RtdEva
   const int l = s_l;
   const double ts = s_ts;
   const double sc = d.scale[(long)c * L + l];
-  const bool antider = ev.antider != 0;
+  constexpr bool deriv = DERIV;
+  const bool antider = !DERIV && ev.antider != 0;
   const double dtop = ts - ts0[l], dbot = ts0[l + 1] - ts;
   const bool beam = d.beam != 0;
   const double mu0 = beam ? d.mu0[c] : 1.0;
@@ -95,6 +100,9 @@ __global__ __launch_bounds__(EVAL_THREADS) void rtd_eval_kernel(RtdDev d, RtdEva
     if (antider) {  // / (scale_tau K), K = -k | +k  (:221-227)
       en /= (-k * sc);
       ep /= (k * sc);
+    } else if (deriv) {  // * (scale_tau K): d/dtau of exp(K dtau*)
+      en *= (-k * sc);
+      ep *= (k * sc);
     }
     // Gp en + Gm ep = [Y (en+ep) - A (en-ep)/k]/T and Gm en + Gp ep = [Y (en+ep) + A (en-ep)/k]/T
     e_s[m * Q + jj] = en + ep;
@@ -103,6 +111,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void rtd_eval_kernel(RtdDev d, RtdEva
   __syncthreads();
   double bfac = beam ? exp(-ts / mu0) : 0.0;
   if (antider) bfac /= (-sc / mu0);
+  else if (deriv) bfac *= (-sc / mu0);
   // u^m_i = sum_j G_ij e_j + B_i exp(-tau*/mu0) (+ v_i for m = 0): NP lanes per (m, stream i); the up- and the
   // down-stream of a quadrature node share the two row sums  P = Y_i . (en+ep),  Qs = A_i . (en-ep)/k
   const int grp = tid / NP, jj = tid % NP;
@@ -128,7 +137,14 @@ __global__ __launch_bounds__(EVAL_THREADS) void rtd_eval_kernel(RtdDev d, RtdEva
     if (d.m0 + d.mstep * (mb + m) == 0 && d.Ns > 0) {  // isotropic-source particular solution (subroutines.py:786-862)
       // The coefficient vectors dq are about the TOP of the layer (rtd_dd.h): v(x) = sum_q dq[q] x^q, x = ts - ts0[l] = dtop.
       const double* dq = d.dq + ((long)c * L + l) * d.Ns * Q;
-      if (!antider) {
+      if (deriv) {  // scale_tau sum_q q dq[q] x^(q-1): the local form as it stands (a derivative has no constant to fix)
+        double tp = sc;
+        for (int q = 1; q < d.Ns; ++q) {
+          vu += q * dq[q * Q + jj] * tp;
+          vd += q * dq[q * Q + NP + jj] * tp;
+          tp *= dtop;
+        }
+      } else if (!antider) {
         double tp = 1.0;
         for (int q = 0; q < d.Ns; ++q) {
           vu += dq[q * Q + jj] * tp;
@@ -210,6 +226,9 @@ __global__ __launch_bounds__(EVAL_THREADS) void rtd_eval_kernel(RtdDev d, RtdEva
       if (antider) {
         direct *= -mu0;
         direct_s /= (-sc / mu0);
+      } else if (deriv) {
+        direct /= -mu0;
+        direct_s *= (-sc / mu0);
       }
     }
     const long o = (long)c * ev.ntau + t;
@@ -344,7 +363,7 @@ __global__ void rtd_export_kernel(RtdDev d, int col, double* GC, double* K, doub
 }  // namespace
 
 void rtd_launch_eval(const RtdDev& d, const RtdEval& e, hipStream_t s) {
-  if (e.um_in != nullptr && e.antider == 0 && rtd_bc_fuses_eval(d)) {  // u^m is there already: sums only
+  if (e.um_in != nullptr && e.antider == 0 && e.deriv == 0 && rtd_bc_fuses_eval(d)) {  // u^m is there already: sums only
     const int ftt = ft_points(d.NP);
     const dim3 g((unsigned)((long)d.C * ((e.ntau + ftt - 1) / ftt)));
     if (d.NP == 4) hipLaunchKernelGGL(rtd_fourier_kernel<4>, g, dim3(EVAL_THREADS), 0, s, d, e);
@@ -366,6 +385,17 @@ void rtd_launch_eval(const RtdDev& d, const RtdEval& e, hipStream_t s) {
   RtdEval e2 = e;
   e2.mchunk = std::min<int>(d.M, (64 << 10) / (int)(2 * 2 * d.NP * sizeof(double)));
   const size_t shm = (size_t)2 * e2.mchunk * 2 * d.NP * sizeof(double);
+  if (e.deriv != 0) {
+    switch (d.NP) {
+      case 4: hipLaunchKernelGGL((rtd_eval_kernel<4, true>), grid, dim3(EVAL_THREADS), shm, s, d, e2); break;
+      case 8: hipLaunchKernelGGL((rtd_eval_kernel<8, true>), grid, dim3(EVAL_THREADS), shm, s, d, e2); break;
+      case 16: hipLaunchKernelGGL((rtd_eval_kernel<16, true>), grid, dim3(EVAL_THREADS), shm, s, d, e2); break;
+      case 32: hipLaunchKernelGGL((rtd_eval_kernel<32, true>), grid, dim3(EVAL_THREADS), shm, s, d, e2); break;
+      case 64: hipLaunchKernelGGL((rtd_eval_kernel<64, true>), grid, dim3(EVAL_THREADS), shm, s, d, e2); break;
+      default: break;
+    }
+    return;
+  }
   switch (d.NP) {
     case 4: hipLaunchKernelGGL(rtd_eval_kernel<4>, grid, dim3(EVAL_THREADS), shm, s, d, e2); break;
     case 8: hipLaunchKernelGGL(rtd_eval_kernel<8>, grid, dim3(EVAL_THREADS), shm, s, d, e2); break;

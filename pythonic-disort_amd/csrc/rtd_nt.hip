@@ -4,7 +4,8 @@
 // (src/PythonicDISORT/pydisort.py:375-698): TMS (:409-596) with its layer prefix/suffix sums (:489-589)
 // and IMS (:601-638).  Two kernels: rtd_nt_tables_kernel builds, per column and stream, the attenuated
 // single-scattering sums contributed by the layers below (up-streams) / above (down-streams) of each layer;
-// rtd_nt_apply_kernel adds rescale * (TMS + IMS) to u at every requested (tau, phi).
+// rtd_nt_apply_kernel adds rescale * (TMS + IMS) to u at every requested (tau, phi) -- or their tau-antiderivatives, or
+// their tau-derivatives (ev.deriv: the factors the antiderivative divides by multiply; the value tables R serve).
 #include "rtd_device.h"
 
 namespace {
@@ -47,6 +48,7 @@ __global__ void rtd_nt_tables_kernel(RtdDev d, RtdNt nt) {
   }
 }
 
+template <bool DV>  // DV: the tau-derivative instance (the other one is the kernel as it was without it)
 __global__ void rtd_nt_apply_kernel(RtdDev d, RtdNt nt, RtdEval ev) {
   const int t = (int)(blockIdx.x % ev.ntau), c = (int)(blockIdx.x / ev.ntau);
   const int N = d.N, L = d.L, Qr = 2 * N;
@@ -60,7 +62,8 @@ __global__ void rtd_nt_apply_kernel(RtdDev d, RtdNt nt, RtdEval ev) {
   const double tb = ts0[l + 1], tt = ts0[l];
   const double mu0 = d.mu0[c], phi0 = d.phi0[c];
   const double I0_4pi = d.I0[c] / (4.0 * M_PI);
-  const bool ad = ev.antider != 0;
+  constexpr bool dv = DV;
+  const bool ad = !DV && ev.antider != 0;
   const double* wfull = nt.wfull + ((long)c * L + l) * nt.nleg_all;
   const double* wtrun = d.wleg + ((long)c * L + l) * d.P;
   const double* ims = nt.ims_coef + (long)c * nt.nleg_all;
@@ -80,12 +83,12 @@ __global__ void rtd_nt_apply_kernel(RtdDev d, RtdNt nt, RtdEval ev) {
     double fac;
     if (up) {
       const double e = exp((ts - tb) / mu - tb / mu0);
-      fac = ad ? att / (-sc / mu0) - e / (sc / mu) : att - e;
-      if (L > 1) fac += R[l] * exp((ts - tb) / mu);
+      fac = ad ? att / (-sc / mu0) - e / (sc / mu) : dv ? att * (-sc / mu0) - e * (sc / mu) : att - e;
+      if (L > 1) fac += dv ? R[l] * exp((ts - tb) / mu) * (sc / mu) : R[l] * exp((ts - tb) / mu);
     } else {
       const double e = exp((tt - ts) / mu - tt / mu0);
-      fac = ad ? att / (-sc / mu0) + e / (sc / mu) : att - e;
-      if (L > 1) fac += R[l] * exp((tt - ts) / mu);
+      fac = ad ? att / (-sc / mu0) + e / (sc / mu) : dv ? att * (-sc / mu0) + e * (sc / mu) : att - e;
+      if (L > 1) fac += dv ? R[l] * exp((tt - ts) / mu) * (-sc / mu) : R[l] * exp((tt - ts) / mu);
     }
     double corr = calB * fac;
     if (!up) {  // IMS, downward streams only (:613-638)
@@ -93,6 +96,8 @@ __global__ void rtd_nt_apply_kernel(RtdDev d, RtdNt nt, RtdEval ev) {
       double chi;
       if (ad)
         chi = ((smu0 - x * smu0 * (smu0 + tau)) * exp(-tau / smu0) - mu * exp(-tau / mu)) / (mu * smu0 * x * x);
+      else if (dv)  // d chi / d tau (chi is a function of the unscaled tau)
+        chi = ((1.0 - (tau - 1.0 / x) / smu0) * exp(-tau / smu0) - exp(-tau / mu) / (mu * x)) / (mu * smu0 * x);
       else
         chi = ((tau - 1.0 / x) * exp(-tau / smu0) + exp(-tau / mu) / x) / (mu * smu0 * x);
       corr += amp * legendre_series(ims, nt.nleg_all, nu) * chi;
@@ -109,5 +114,7 @@ void rtd_launch_nt_tables(const RtdDev& d, const RtdNt& nt, hipStream_t s) {
 }
 
 void rtd_launch_nt_apply(const RtdDev& d, const RtdNt& nt, const RtdEval& e, hipStream_t s) {
-  hipLaunchKernelGGL(rtd_nt_apply_kernel, dim3((unsigned)((long)e.ntau * d.C)), dim3(128), 0, s, d, nt, e);
+  const dim3 grid((unsigned)((long)e.ntau * d.C));
+  if (e.deriv != 0) hipLaunchKernelGGL(rtd_nt_apply_kernel<true>, grid, dim3(128), 0, s, d, nt, e);
+  else hipLaunchKernelGGL(rtd_nt_apply_kernel<false>, grid, dim3(128), 0, s, d, nt, e);
 }

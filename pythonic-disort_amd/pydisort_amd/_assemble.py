@@ -11,7 +11,8 @@ reference itself (tests/golden/assemble/*.npz, tests/golden/make_assemble_golden
 
 Arguments that only steer the reference's own solver -- ``M_inv`` (recomputed), ``NQuad``, ``is_atmos_multilayered``,
 ``I0_div_4pi``, ``use_banded_solver_NLayers`` -- are accepted and checked for consistency where cheap; ``autograd_compatible``
-must be False (out of scope).
+must be False (no autograd tracing: the tau-derivatives it exists for come from the returned callables' keyword
+``is_derivative_wrt_tau``).
 """
 import numpy as np
 
@@ -59,7 +60,8 @@ def _assemble_intensity_and_fluxes(
     device=0,
 ):
     if autograd_compatible:
-        raise NotImplementedError("autograd_compatible=True is outside the scope of the HIP path.")
+        raise NotImplementedError("autograd_compatible=True is outside the scope of the HIP path; for tau-derivatives call "
+                                  "the returned functions with is_derivative_wrt_tau=True.")
     N, NQuad, NLeg, NFourier, NLayers, NBDRF = int(N), int(NQuad), int(NLeg), int(NFourier), int(NLayers), int(NBDRF)
     if NQuad != 2 * N or NQuad > 128:
         raise ValueError("Need NQuad = 2 N <= 128.")

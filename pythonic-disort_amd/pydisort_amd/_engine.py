@@ -177,9 +177,13 @@ class Plan:
         _lib.check(_lib.load().rtd_pool_set_limit(int(nbytes), int(device), C.byref(b)))
         return b.value
 
-    def evaluate(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False):
+    def evaluate(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
         """tau [C, ntau]; phi [nphi] or None -> dict of arrays (u [C,Q,ntau,nphi], u0 [C,Q,ntau],
-        flux_up / flux_down_diffuse / flux_down_direct [C,ntau], ulast [C,Q,ntau])."""
+        flux_up / flux_down_diffuse / flux_down_direct [C,ntau], ulast [C,Q,ntau]).  derivative: every output is its
+        derivative with respect to the unscaled tau (include/rtd.h: bit 2 of rtd_plan_evaluate's flag word; one-sided from above
+        at an interface); not together with antiderivative."""
+        if antiderivative and derivative:
+            raise ValueError("antiderivative and derivative exclude each other.")
         tau = _f64(np.atleast_2d(tau))
         assert tau.shape[0] == self.C
         ntau = tau.shape[1]
@@ -192,7 +196,8 @@ class Plan:
         fl = [np.empty((self.C, ntau)) for _ in range(3)] if "flux" in want else [None] * 3
         out.update(u=u, u0=u0, ulast=ul, flux_up=fl[0], flux_down_diffuse=fl[1], flux_down_direct=fl[2])
         self._checked(self._lib.rtd_plan_evaluate(self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi),
-                                                  int(bool(antiderivative)) | (2 if skip_nt else 0), _lib.dptr(u),
+                                                  int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0),
+                                                  _lib.dptr(u),
                                                   _lib.dptr(u0),
                                                   _lib.dptr(fl[0]), _lib.dptr(fl[1]), _lib.dptr(fl[2]),
                                                   _lib.dptr(ul)), out)
@@ -205,6 +210,13 @@ class Plan:
         self._ev_shape = (tau.shape[1], len(phi))
         _lib.check(self._lib.rtd_plan_set_eval_points(self._h, tau.shape[1], _lib.dptr(tau), len(phi),
                                                       _lib.dptr(phi)))
+
+    def set_eval_order(self, order):
+        """What run() / run_fetch() evaluate at the stored points: 0 the values (default), -1 their tau-antiderivatives, +1 their
+        tau-derivatives (include/rtd.h: rtd_plan_set_eval_order)."""
+        if order not in (-1, 0, 1):
+            raise ValueError("order must be -1, 0 or +1.")
+        _lib.check(self._lib.rtd_plan_set_eval_order(self._h, int(order)))
 
     def run(self):
         _lib.check(self._lib.rtd_plan_run(self._h))

@@ -11,7 +11,12 @@ DEFAULT_RETAIN_BYTES = 16 << 30  # pydisort_batch(retain=..., retain_bytes=None)
 
 
 class BatchSolution:
-    """Evaluators over all columns; arrays carry a leading column axis."""
+    """Evaluators over all columns; arrays carry a leading column axis.
+
+    ``is_derivative_wrt_tau=True`` (keyword-only) returns the derivative with respect to the unscaled ``tau`` of what the
+    evaluator returns otherwise -- exact, from the closed form, for the whole batch in one device pass; at an interface it is the
+    one-sided derivative from above (of the layer that ends there), at ``tau = 0`` the right derivative.  It excludes
+    ``is_antiderivative_wrt_tau`` (``ValueError``)."""
 
     def __init__(self, plan, prep):
         self.plan, self.prep = plan, prep
@@ -25,21 +30,31 @@ class BatchSolution:
             raise ValueError("tau input outside the tau range specified for the atmosphere (check `tau_arr`).")
         return np.ascontiguousarray(tau)
 
-    def u(self, tau, phi, is_antiderivative_wrt_tau=False):
+    @staticmethod
+    def _order(is_antiderivative_wrt_tau, is_derivative_wrt_tau):
+        if is_derivative_wrt_tau and is_antiderivative_wrt_tau:
+            raise ValueError("`is_derivative_wrt_tau` and `is_antiderivative_wrt_tau` cannot both be set.")
+        return bool(is_derivative_wrt_tau)
+
+    def u(self, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> [C, NQuad, ntau, nphi]"""
-        return self.plan.evaluate(self._tau(tau), phi, is_antiderivative_wrt_tau, want=("u",))["u"]
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        return self.plan.evaluate(self._tau(tau), phi, is_antiderivative_wrt_tau, want=("u",), derivative=deriv)["u"]
 
-    def u0(self, tau, is_antiderivative_wrt_tau=False):
+    def u0(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> [C, NQuad, ntau]"""
-        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("u0",))["u0"]
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("u0",), derivative=deriv)["u0"]
 
-    def flux_up(self, tau, is_antiderivative_wrt_tau=False):
+    def flux_up(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> [C, ntau]"""
-        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("flux",))["flux_up"]
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)["flux_up"]
 
-    def flux_down(self, tau, is_antiderivative_wrt_tau=False):
+    def flux_down(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> (diffuse [C, ntau], direct [C, ntau])"""
-        r = self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("flux",))
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        r = self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)
         return r["flux_down_diffuse"], r["flux_down_direct"]
 
 
@@ -189,7 +204,8 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
     return sol.mu_arr, sol
 
 
-def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=False, out=None, numeric_errors="raise"):
+def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=False, out=None, numeric_errors="raise",
+                           *, tau_order=0):
     """Throughput form for large column counts: ONE plan holds the inputs and the results of all columns, the
     intermediates of the solve (~8 MB per cfg4 column) live for `chunk_columns` columns at a time (0: ~8 192 (column,
     mode) chains per window) and the device-to-host copies of a window overlap the kernels of the next (``Plan.run_fetch``).
@@ -200,7 +216,12 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
     tau : [C, ntau] evaluation depths; phi : [nphi].
     out : optional dict of preallocated C-contiguous float64 result arrays to fill (the same keys and shapes).
     numeric_errors : as in ``pydisort_batch`` ("nan": failed columns come back as NaN, the rest of the batch is kept).
+    tau_order : 0 the values (default), +1 their derivatives with respect to the unscaled tau (as ``is_derivative_wrt_tau`` of the
+          evaluators: one-sided from above at an interface), -1 their tau-antiderivatives (``is_antiderivative_wrt_tau``): a
+          batch too large to retain gets them host to host through the same window pipeline (``Plan.set_eval_order``).
     Returns dict(u [C, NQuad, ntau, nphi] (absent when only_flux), u0, flux_up, flux_down_diffuse, flux_down_direct)."""
+    if tau_order not in (-1, 0, 1):
+        raise ValueError("tau_order must be -1, 0 or +1.")
     tau = np.ascontiguousarray(np.asarray(tau, float))
     C, ntau = tau.shape
     if chunk_columns <= 0:
@@ -217,6 +238,8 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
         sol._tau(tau)  # range check on the host, with the reference's message
         phi = np.array([0.0]) if only_flux else np.atleast_1d(np.asarray(phi, float))
         plan.set_eval_points(tau, phi)
+        if tau_order != 0:
+            plan.set_eval_order(tau_order)
         Q = plan.Q
         shapes = dict(u0=(C, Q, ntau), flux_up=(C, ntau), flux_down_diffuse=(C, ntau), flux_down_direct=(C, ntau))
         if not only_flux:

@@ -116,7 +116,9 @@ def pydisort(
     """Solve the 1D plane-parallel RTE for one atmospheric column; see the reference's docstring
     (pydisort.py:30-128) for the meaning of every argument.  Returns ``(mu_arr, flux_up, flux_down,
     u0[, u])``.  ``use_banded_solver_NLayers`` is validated and otherwise ignored (the device solver is
-    a single block-banded elimination); ``autograd_compatible=True`` is not supported."""
+    a single block-banded elimination).  ``autograd_compatible=True`` is not supported and raises ``NotImplementedError``: what
+    the reference offers it for, the ``tau``-derivatives of the output functions, every returned callable gives directly with
+    the keyword ``is_derivative_wrt_tau=True`` (exact, from the closed form of the solution; see ``_Closures``)."""
     if autograd_compatible:
         raise NotImplementedError("autograd_compatible=True is not available in the MI355X build.")
     tau_arr = np.atleast_1d(np.asarray(tau_arr, dtype=float))
@@ -247,7 +249,22 @@ def pydisort(
 
 
 class _Closures:
-    """The returned callables.  They keep the device plan (GC, K, B ... stay in HBM) alive."""
+    """The returned callables.  They keep the device plan (GC, K, B ... stay in HBM) alive.
+
+    Beyond the reference's parameters every callable takes the keyword-only ``is_derivative_wrt_tau``: the result is then the
+    derivative with respect to ``tau`` (the caller's unscaled optical depth) of what the callable returns otherwise, evaluated
+    in closed form on the device.  The layer of a point is looked up as for the values (``argmax(tau <= tau_arr)``): at an
+    interface ``tau = tau_arr[l]`` the derivative is the one-sided one from above (of layer ``l``, which ends there), at
+    ``tau = 0`` the right derivative; derivatives are in general discontinuous across interfaces.  It excludes
+    ``is_antiderivative_wrt_tau`` and ``return_Fourier_error`` (``ValueError``)."""
+
+    @staticmethod
+    def _order(is_antiderivative_wrt_tau, is_derivative_wrt_tau, return_Fourier_error=False):
+        if is_derivative_wrt_tau and is_antiderivative_wrt_tau:
+            raise ValueError("`is_derivative_wrt_tau` and `is_antiderivative_wrt_tau` cannot both be set.")
+        if is_derivative_wrt_tau and return_Fourier_error:
+            raise ValueError("`return_Fourier_error` is not available together with `is_derivative_wrt_tau`.")
+        return bool(is_derivative_wrt_tau)
 
     def __init__(self, plan, prep, tau_arr, M, beam, mu0, I0_user):
         self.plan, self.prep, self.tau_arr, self.M, self.beam = plan, prep, tau_arr, M, beam
@@ -266,10 +283,11 @@ class _Closures:
         return tau
 
     def u(self, tau, phi, is_antiderivative_wrt_tau=False, return_Fourier_error=False, return_tau_arr=False,
-          *, _return_l=False):
+          *, _return_l=False, is_derivative_wrt_tau=False):
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau, return_Fourier_error)
         tau = self._tau(tau)
         phi = np.atleast_1d(np.asarray(phi, dtype=float))
-        r = self.plan.evaluate(tau[None], phi, is_antiderivative_wrt_tau, want=("u",))
+        r = self.plan.evaluate(tau[None], phi, is_antiderivative_wrt_tau, want=("u",), derivative=deriv)
         outs = (np.squeeze(r["u"][0]),)
         if return_Fourier_error:  # _assemble.py:264-318; measured on the uncorrected delta-M solution (pydisort.py:652-660)
             r = self.plan.evaluate(tau[None], phi, is_antiderivative_wrt_tau, want=("u", "ulast"), skip_nt=True)
@@ -282,9 +300,11 @@ class _Closures:
             outs += (np.argmax(tau[:, None] <= self.tau_arr[None, :], axis=1),)
         return outs if len(outs) > 1 else outs[0]
 
-    def u0(self, tau, is_antiderivative_wrt_tau=False, return_tau_arr=False, _return_act_dscale_for_reclass=False):
+    def u0(self, tau, is_antiderivative_wrt_tau=False, return_tau_arr=False, _return_act_dscale_for_reclass=False,
+           *, is_derivative_wrt_tau=False):
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         tau = self._tau(tau)
-        r = self.plan.evaluate(tau[None], None, is_antiderivative_wrt_tau, want=("u0",))
+        r = self.plan.evaluate(tau[None], None, is_antiderivative_wrt_tau, want=("u0",), derivative=deriv)
         outs = (np.squeeze(r["u0"][0]),)
         if return_tau_arr:
             outs += (self.tau_arr,)
@@ -296,6 +316,9 @@ class _Closures:
                 if is_antiderivative_wrt_tau:
                     rec = (self.I0_user * np.exp(-ts / self.mu0) / (-p["scale_tau"][0, l] / self.mu0)
                            - self.I0_user * np.exp(-tau / self.mu0) * -self.mu0)
+                elif deriv:
+                    rec = (self.I0_user * np.exp(-ts / self.mu0) * (-p["scale_tau"][0, l] / self.mu0)
+                           - self.I0_user * np.exp(-tau / self.mu0) / -self.mu0)
                 else:
                     rec = self.I0_user * np.exp(-ts / self.mu0) - self.I0_user * np.exp(-tau / self.mu0)
             else:
@@ -303,15 +326,17 @@ class _Closures:
             outs += (rec,)
         return outs if len(outs) > 1 else outs[0]
 
-    def flux_up(self, tau, is_antiderivative_wrt_tau=False, return_tau_arr=False):
+    def flux_up(self, tau, is_antiderivative_wrt_tau=False, return_tau_arr=False, *, is_derivative_wrt_tau=False):
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         tau = self._tau(tau)
-        r = self.plan.evaluate(tau[None], None, is_antiderivative_wrt_tau, want=("flux",))
+        r = self.plan.evaluate(tau[None], None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)
         out = np.squeeze(r["flux_up"][0])[()]
         return (out, self.tau_arr) if return_tau_arr else out
 
-    def flux_down(self, tau, is_antiderivative_wrt_tau=False, return_tau_arr=False):
+    def flux_down(self, tau, is_antiderivative_wrt_tau=False, return_tau_arr=False, *, is_derivative_wrt_tau=False):
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         tau = self._tau(tau)
-        r = self.plan.evaluate(tau[None], None, is_antiderivative_wrt_tau, want=("flux",))
+        r = self.plan.evaluate(tau[None], None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)
         # without a beam source the reference's direct flux is the scalar 0 (_assemble.py:568-570, :610)
         direct = np.squeeze(r["flux_down_direct"][0])[()] if self.beam else np.float64(0.0)
         outs = (np.squeeze(r["flux_down_diffuse"][0])[()], direct)

@@ -92,21 +92,24 @@ def atleast_2d_append(*arys):
 
 def generate_diff_act_flux_funcs(u0):
     """Up and down diffuse actinic flux functions from the zeroth intensity mode ``u0`` returned by ``pydisort``,
-    with the reclassification of delta-scaled actinic flux (:258-318)."""
+    with the reclassification of delta-scaled actinic flux (:258-318).  The keyword-only ``is_derivative_wrt_tau`` of the
+    returned functions goes through to ``u0`` (the tau-derivative of the actinic fluxes, reclassification term included)."""
     N = len(u0(0)) // 2
     wts = Gauss_Legendre_quad(N)[1]
 
-    def flux_act_up(tau, is_antiderivative_wrt_tau=False, return_tau_arr=False):
+    def flux_act_up(tau, is_antiderivative_wrt_tau=False, return_tau_arr=False, *, is_derivative_wrt_tau=False):
+        kw = {"is_derivative_wrt_tau": True} if is_derivative_wrt_tau else {}  # (a u0 without the keyword still serves the rest)
         if return_tau_arr:
-            val, tau_arr = u0(tau, is_antiderivative_wrt_tau, True)
+            val, tau_arr = u0(tau, is_antiderivative_wrt_tau, True, **kw)
             return np.squeeze(2 * pi * wts @ val[:N])[()], tau_arr
-        return np.squeeze(2 * pi * wts @ u0(tau, is_antiderivative_wrt_tau)[:N])[()]
+        return np.squeeze(2 * pi * wts @ u0(tau, is_antiderivative_wrt_tau, **kw)[:N])[()]
 
-    def flux_act_down_diffuse(tau, is_antiderivative_wrt_tau=False, return_tau_arr=False):
+    def flux_act_down_diffuse(tau, is_antiderivative_wrt_tau=False, return_tau_arr=False, *, is_derivative_wrt_tau=False):
+        kw = {"is_derivative_wrt_tau": True} if is_derivative_wrt_tau else {}
         if return_tau_arr:
-            val, tau_arr, reclass = u0(tau, is_antiderivative_wrt_tau, True, _return_act_dscale_for_reclass=True)
+            val, tau_arr, reclass = u0(tau, is_antiderivative_wrt_tau, True, _return_act_dscale_for_reclass=True, **kw)
             return np.squeeze(2 * pi * wts @ val[N:] + reclass)[()], tau_arr
-        val, reclass = u0(tau, is_antiderivative_wrt_tau, False, _return_act_dscale_for_reclass=True)
+        val, reclass = u0(tau, is_antiderivative_wrt_tau, False, _return_act_dscale_for_reclass=True, **kw)
         return np.squeeze(2 * pi * wts @ val[N:] + reclass)[()]
 
     return flux_act_up, flux_act_down_diffuse
