@@ -22,8 +22,10 @@ def _nu(mu, phi, mu0, phi0):
     return (-mu0 * mu)[:, None] + (np.sqrt(1 - mu0**2) * np.sqrt(1 - mu**2))[:, None] * np.cos(phi0 - phi)[None, :]
 
 
-def tms(sol, tau, l, ts, phi, antider):
-    """TMS correction [Q, Ntau, Nphi] (pydisort.py:409-596)."""
+def tms(sol, tau, l, ts, phi, antider, deriv=False):
+    """TMS correction [Q, Ntau, Nphi] (pydisort.py:409-596); deriv: its tau-derivative (no counterpart in the reference: every
+    term is an exponential in tau*, d tau*/d tau = scale_tau of the point's layer; the other layers' tables are the value-form
+    ones)."""
     p = sol.p
     N, L, mu, mu0 = p["N"], p["L"], p["mu"], p["mu0"]
     ts0, dts, sc = p["tau_s0"], p["thick_s"], p["scale_tau"]
@@ -43,6 +45,10 @@ def tms(sol, tau, l, ts, phi, antider):
         c0 = beam_att / (-sc[l] / mu0)
         up = c0[None, :] - np.exp((ts - tb)[None, :] / mu[:, None] - tb[None, :] / mu0) / (sc[l][None, :] / mu[:, None])
         dn = c0[None, :] + np.exp((tt - ts)[None, :] / mu[:, None] - tt[None, :] / mu0) / (sc[l][None, :] / mu[:, None])
+    elif deriv:
+        c0 = beam_att * (-sc[l] / mu0)
+        up = c0[None, :] - np.exp((ts - tb)[None, :] / mu[:, None] - tb[None, :] / mu0) * (sc[l][None, :] / mu[:, None])
+        dn = c0[None, :] + np.exp((tt - ts)[None, :] / mu[:, None] - tt[None, :] / mu0) * (sc[l][None, :] / mu[:, None])
     else:  # :471-479
         up = beam_att[None, :] - np.exp((ts - tb)[None, :] / mu[:, None] - tb[None, :] / mu0)
         dn = beam_att[None, :] - np.exp((tt - ts)[None, :] / mu[:, None] - tt[None, :] / mu0)
@@ -66,13 +72,15 @@ def tms(sol, tau, l, ts, phi, antider):
                 tneg = -intf[:, r] * tneg
             for ll in range(r + 1, L):
                 Rneg[:, ll] += tneg * np.exp(-(ts0[ll] - ts0[r + 1]) / mu)
-        inlayer[:N] += Rpos[:, l] * np.exp((ts - tb)[None, :] / mu[:, None])
-        inlayer[N:] += Rneg[:, l] * np.exp((tt - ts)[None, :] / mu[:, None])
+        rate = (sc[l][None, :] / mu[:, None]) if deriv else np.ones((N, len(l)))
+        inlayer[:N] += Rpos[:, l] * np.exp((ts - tb)[None, :] / mu[:, None]) * rate
+        inlayer[N:] += Rneg[:, l] * np.exp((tt - ts)[None, :] / mu[:, None]) * (-rate if deriv else rate)
     return calB[:, l, :] * inlayer[:, :, None]
 
 
-def ims(sol, tau, phi, antider):
-    """IMS correction for the downward streams [N, Ntau, Nphi] (pydisort.py:601-638)."""
+def ims(sol, tau, phi, antider, deriv=False):
+    """IMS correction for the downward streams [N, Ntau, Nphi] (pydisort.py:601-638); deriv: d chi / d tau (chi is a function of
+    the unscaled tau)."""
     p = sol.p
     mu, mu0 = p["mu"], p["mu0"]
     w = p["omega"] * p["tau"]
@@ -87,6 +95,9 @@ def ims(sol, tau, phi, antider):
     if antider:
         chi = ((smu0 - x[:, None] * smu0 * (smu0 + tau)[None, :]) * np.exp(-tau / smu0)[None, :]
                - mu[:, None] * np.exp(-tau[None, :] / mu[:, None])) / (mu * smu0 * x**2)[:, None]
+    elif deriv:
+        chi = ((1 - (tau[None, :] - 1 / x[:, None]) / smu0) * np.exp(-tau / smu0)[None, :]
+               - np.exp(-tau[None, :] / mu[:, None]) / (mu * x)[:, None]) / (mu * smu0 * x)[:, None]
     else:
         chi = ((tau[None, :] - 1 / x[:, None]) * np.exp(-tau / smu0)[None, :]
                + np.exp(-tau[None, :] / mu[:, None]) / x[:, None]) / (mu * smu0 * x)[:, None]
@@ -99,13 +110,15 @@ def corrected_u(sol):
     """The closure the reference returns as ``u`` when the corrections are active (:643-694)."""
     p = sol.p
 
-    def u_corrected(tau, phi, is_antiderivative_wrt_tau=False, return_Fourier_error=False, return_tau_arr=False):
+    def u_corrected(tau, phi, is_antiderivative_wrt_tau=False, return_Fourier_error=False, return_tau_arr=False, *,
+                    is_derivative_wrt_tau=False):
         tau_a = np.atleast_1d(np.asarray(tau, dtype=float))
         phi_a = np.atleast_1d(np.asarray(phi, dtype=float))
-        base = sol.u(tau_a, phi_a, is_antiderivative_wrt_tau, return_Fourier_error, return_tau_arr)
+        base = sol.u(tau_a, phi_a, is_antiderivative_wrt_tau, return_Fourier_error, return_tau_arr,
+                     is_derivative_wrt_tau=is_derivative_wrt_tau)
         _, l, ts = sol._locate(tau_a)
-        corr = tms(sol, tau_a, l, ts, phi_a, is_antiderivative_wrt_tau)
-        corr[p["N"]:] += ims(sol, tau_a, phi_a, is_antiderivative_wrt_tau)
+        corr = tms(sol, tau_a, l, ts, phi_a, is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        corr[p["N"]:] += ims(sol, tau_a, phi_a, is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         corr = p["rescale"] * np.squeeze(corr)
         if isinstance(base, tuple):
             return (base[0] + corr,) + base[1:]
