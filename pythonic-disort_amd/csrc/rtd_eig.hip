@@ -54,6 +54,27 @@ __device__ __forceinline__ double xor_lane(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// `old` with the lanes of the banks in BANK (bit b: the lanes 4 b .. 4 b + 3 of every 16-lane DPP row) replaced by the value `src`
+// has in the lane the DPP control CTRL names: one v_mov_b32_dpp per dword that merges into `old` in place -- a lane select and
+// a cross-lane move in one instruction, for lane predicates that are whole banks (lane & 8, lane & 4).
+// Controls: row_ror:8 = 0x128 (lane ^ 8), row_shr:4 = 0x114 (lane - 4), row_shl:4 = 0x104 (lane + 4).
+template <int CTRL, int BANK>
+__device__ __forceinline__ double dpp_merge(const double old, const double src) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xF, BANK, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xF, BANK, false);
+  return __hiloint2double(hi, lo);
+}
+
+// Two values that each take some lanes from the other (an exchange) need one copy: a single 64-bit move, made here so that the
+// compiler does not split it into two 32-bit ones; the merge then happens in place on the copy.  The compiler's hazard recogniser
+// does not see this VALU write and the copy becomes the `old` operand of a DPP move: the two wait states such a read may need are
+// spent here (tools/check_dpp_hazards.py looks at v_fmac_f64_dpp writes only).
+__device__ __forceinline__ double copy64(const double v) {
+  double c;
+  asm("v_mov_b64 %0, %1\n\ts_nop 1" : "=v"(c) : "v"(v));
+  return c;
+}
+
 constexpr __host__ __device__ int high_bit(int t) {
   int b = 1;
   while ((b << 1) <= t) b <<= 1;
@@ -92,6 +113,16 @@ __device__ __forceinline__ double approx_rcp(double x) {
 #define RTD_CHOL_FMAC_DPP 1  /* Cholesky trailing updates as ONE v_fmac_f64_dpp (row_newbcast) per element, NP = 16 */
 #endif
 
+#ifndef RTD_DPP_MERGE
+#define RTD_DPP_MERGE 1  /* NP = 16: levels 8 and 4 of the transposed reductions and the pair-layout exchange as bank-masked DPP merges (dpp_merge) */
+#endif
+#ifndef RTD_CHOL_EXEC_PICK
+#define RTD_CHOL_EXEC_PICK 1  /* NP = 16: a Cholesky step's multiplier and diagonal under constant EXEC masks (chol_pick16), no compare or select */
+#endif
+
+constexpr bool kDppMerge = RTD_DPP_MERGE != 0;
+constexpr bool kCholPick16 = RTD_CHOL_FMAC_DPP != 0 && RTD_CHOL_EXEC_PICK != 0;
+
 #ifndef RTD_EIGEN32_WAVES
 #define RTD_EIGEN32_WAVES 2  /* waves per SIMD of the 64-stream eigen kernel (256 VGPRs; the spill counts of every kernel: profiles/rNN_kernel_resources.json, tools/kernel_resources.py; 1: 278 VGPRs) */
 #endif
@@ -118,9 +149,18 @@ __device__ __forceinline__ double approx_rcp(double x) {
 // lower half of the second -- afterwards first + second is the level's result in every lane.  (O = 16 and 32 were ds_swizzle /
 // ds_bpermute exchanges behind two selects; their latency-hiding schedule held both operand sets of every element at once: the beam
 // stage of the 64-stream kernel was where its 68-110 spilled registers came from.)
-template <int O, bool SWAP>
+// MERGE (the 16-stream-group kernel, O = 8 and 4: the lanes with (lane & O) are whole banks): the two operands of the level's add are
+// formed in place by bank-masked DPP moves -- `lo` with the partner's hi in the hi lanes, `hi` with the partner's lo in the lo lanes
+// -- six instructions per double (one is the copy an exchange needs, copy64) and no select, instead of four selects, two moves
+// (ds_swizzle at O = 4) and the add.  Every lane adds the same two values as in the select form (the hi lanes in the other order):
+// the same bits.  O = 2 and 1 split a bank and keep the select form.
+template <int O, bool SWAP, bool MERGE = false>
 __device__ __forceinline__ double level_add(const double lo, const double hi, const bool is_hi) {
-  if constexpr (SWAP && (O == 16 || O == 32)) {
+  if constexpr (MERGE && O == 8) {
+    return dpp_merge<0x128, 0xC>(copy64(lo), hi) + dpp_merge<0x128, 0x3>(hi, lo);
+  } else if constexpr (MERGE && O == 4) {
+    return dpp_merge<0x114, 0xA>(copy64(lo), hi) + dpp_merge<0x104, 0x5>(hi, lo);
+  } else if constexpr (SWAP && (O == 16 || O == 32)) {
     typedef unsigned int u2 __attribute__((ext_vector_type(2)));
     u2 a, b;
     if constexpr (O == 16) {
@@ -139,23 +179,23 @@ __device__ __forceinline__ double level_add(const double lo, const double hi, co
 
 // Transposed reduction: every lane enters with NP terms v[0..NP) (term i belongs to row i) and leaves with the sum of
 // row `j` over the NP lanes of its group -- NP-1 exchange-adds in registers, no LDS memory.
-template <int NP, int O>
+template <int NP, int O, bool MERGE = false>
 struct TransposeStep {
   static __device__ __forceinline__ void run(double (&v)[NP], const int j) {
     const bool hi = (j & O) != 0;
 #pragma unroll
-    for (int i = 0; i < O; ++i) v[i] = level_add<O, NP == 32>(v[i], v[i + O], hi);  // (the 128-stream kernel keeps its ds_bpermute form:
+    for (int i = 0; i < O; ++i) v[i] = level_add<O, NP == 32, MERGE>(v[i], v[i + O], hi);  // (the 128-stream kernel keeps its ds_bpermute form:
     //                                                                                 with the swaps it spilled 123 registers and ran 3.7 x slower)
-    TransposeStep<NP, O / 2>::run(v, j);
+    TransposeStep<NP, O / 2, MERGE>::run(v, j);
   }
 };
-template <int NP>
-struct TransposeStep<NP, 0> {
+template <int NP, bool MERGE>
+struct TransposeStep<NP, 0, MERGE> {
   static __device__ __forceinline__ void run(double (&)[NP], const int) {}
 };
-template <int NP>
+template <int NP, bool MERGE = false>  // MERGE: see level_add (the 16-stream-group kernel only)
 __device__ __forceinline__ double transpose_reduce(double (&v)[NP], const int j) {
-  TransposeStep<NP, NP / 2>::run(v, j);
+  TransposeStep<NP, NP / 2, MERGE>::run(v, j);
   return v[0];
 }
 
@@ -230,12 +270,49 @@ struct CholRowDpp<NP, K, NP, ORDERED> {
   static __device__ __forceinline__ void run(double (&)[NP], const double) {}
 };
 
+// Step K's multiplier and diagonal for a group of 16 lanes without a compare or a select: the lanes j > K form f = colk * r under
+// an EXEC mask that is a compile-time constant of the step, lane K takes f = 0 and the pivot as its diagonal under a second one
+// (v_mov_b64: one instruction per double); the lanes j < K are not written and keep the f = 0 they took at their own step.  EXEC
+// is written by SALU moves only (no wait states before the VALU instructions that follow) and is restored inside the statement.
+// The lanes j > K also clear colk, their element above the diagonal, which nothing reads after this step: the scaling that ends
+// the factorisation is then one multiplication per element, with no compare and no select (0 * rinv = 0).
+template <int K, bool LAST>
+__device__ __forceinline__ void chol_pick16(double& f, double& diag, double& colk, const double r, const double akk) {
+  constexpr int GT = (int)(((0xFFFFu << (K + 1)) & 0xFFFFu) * 0x10001u), EQ = (int)((1u << K) * 0x10001u);
+  unsigned long long saved;
+  if constexpr (LAST)  // no rows below the pivot: the diagonal only
+    asm("s_mov_b64 %[sv], exec\n\t"
+        "s_mov_b32 exec_lo, %[eq]\n\t"
+        "s_mov_b32 exec_hi, %[eq]\n\t"
+        "v_mov_b64 %[d], %[a]\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(saved), [d] "+v"(diag)
+        : [a] "v"(akk), [eq] "n"(EQ));
+  else
+    asm("s_mov_b64 %[sv], exec\n\t"
+        "s_mov_b32 exec_lo, %[gt]\n\t"
+        "s_mov_b32 exec_hi, %[gt]\n\t"
+        "v_mul_f64 %[f], %[c], %[r]\n\t"
+        "v_mov_b64 %[c], 0\n\t"
+        "s_mov_b32 exec_lo, %[eq]\n\t"
+        "s_mov_b32 exec_hi, %[eq]\n\t"
+        "v_mov_b64 %[f], 0\n\t"
+        "v_mov_b64 %[d], %[a]\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(saved), [f] "+v"(f), [d] "+v"(diag), [c] "+v"(colk)
+        : [r] "v"(r), [a] "v"(akk), [gt] "n"(GT), [eq] "n"(EQ));
+}
+
 template <int NP, int K>
 struct CholStep {
-  static __device__ __forceinline__ void run(double (&col)[NP], double& diag, const int j) {
+  static __device__ __forceinline__ void run(double (&col)[NP], double& diag, double& f, const int j) {
     const double akk = bcast_lane<NP, K>(col[K]);
-    const double f = (j > K) ? col[K] * fast_rcp(akk) : 0.0;
-    diag = (j == K) ? akk : diag;
+    if constexpr (kCholPick16 && NP == 16) {
+      chol_pick16<K, K == NP - 1>(f, diag, col[K], fast_rcp(akk), akk);
+    } else {
+      f = (j > K) ? col[K] * fast_rcp(akk) : 0.0;
+      diag = (j == K) ? akk : diag;
+    }
     if constexpr (RTD_CHOL_FMAC_DPP && NP == 16) {
       // col[i] -= bcast_K(col[i]) * f in one instruction: the DP-ALU DPP form exists for row_newbcast only (the DPP
       // source is the accumulator itself).  A VALU write of a VGPR needs two wait states before a DPP read of it: the
@@ -245,12 +322,12 @@ struct CholStep {
 #pragma unroll
       for (int i = K + 1; i < NP; ++i) col[i] = fma(-bcast_lane<NP, K>(col[i]), f, col[i]);
     }
-    CholStep<NP, K + 1>::run(col, diag, j);
+    CholStep<NP, K + 1>::run(col, diag, f, j);
   }
 };
 template <int NP>
 struct CholStep<NP, NP> {
-  static __device__ __forceinline__ void run(double (&)[NP], double&, const int) {}
+  static __device__ __forceinline__ void run(double (&)[NP], double&, double&, const int) {}
 };
 // acc[I] += bcast_I(y0) * coef and acc[16 + I] += bcast_I(y1) * coef for I = 0..15: lane I of the caller's DPP row supplies the
 // multiplier (row_newbcast), one v_fmac_f64_dpp per term
@@ -473,11 +550,14 @@ __device__ __forceinline__ double cholesky_columns32(double (&col)[32], const in
 
 template <int NP>
 __device__ __forceinline__ double cholesky_columns(double (&col)[NP], const int j) {
-  double diag = 1.0;
-  CholStep<NP, 0>::run(col, diag, j);
+  double diag = 1.0, f = 0.0;  // (f: the step's multiplier, carried from step to step at NP = 16 -- chol_pick16)
+  CholStep<NP, 0>::run(col, diag, f, j);
   const double rinv = fast_rsqrt(diag);
 #pragma unroll
-  for (int i = 0; i < NP; ++i) col[i] = (i >= j) ? col[i] * rinv : 0.0;
+  for (int i = 0; i < NP; ++i) {
+    if constexpr (kCholPick16 && NP == 16) col[i] *= rinv;  // (zero above the diagonal since step i: chol_pick16)
+    else col[i] = (i >= j) ? col[i] * rinv : 0.0;
+  }
   return rinv;
 }
 
@@ -1138,9 +1218,14 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     double xh[H], yh[H];
 #pragma unroll
     for (int i = 0; i < H; ++i) {  // columns p and p + H start in slot p: trade the halves with lane ^ H
-      const double recv = xor_lane<H>(u ? w[i] : w[H + i]);
-      xh[i] = u ? recv : w[i];
-      yh[i] = u ? w[H + i] : recv;
+      if constexpr (kDppMerge && NP == 16) {  // u is the lane's bit 3, two whole banks: merged in place by bank-masked moves, no select (dpp_merge)
+        xh[i] = dpp_merge<0x128, 0xC>(copy64(w[i]), w[H + i]);
+        yh[i] = dpp_merge<0x128, 0x3>(w[H + i], w[i]);
+      } else {
+        const double recv = xor_lane<H>(u ? w[i] : w[H + i]);
+        xh[i] = u ? recv : w[i];
+        yh[i] = u ? w[H + i] : recv;
+      }
     }
     int ix = p, iy = p + H;  // the columns' starting indices travel with them
     for (int sweep = 0; sweep < 40; ++sweep) {
@@ -1173,9 +1258,14 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     // back to one column per lane: lane (p, 0) takes column X of its slot, lane (p, 1) column Y ...
 #pragma unroll
     for (int i = 0; i < H; ++i) {
-      const double recv = xor_lane<H>(u ? xh[i] : yh[i]);
-      w[i] = u ? recv : xh[i];
-      w[H + i] = u ? yh[i] : recv;
+      if constexpr (kDppMerge && NP == 16) {
+        w[i] = dpp_merge<0x128, 0xC>(copy64(xh[i]), yh[i]);
+        w[H + i] = dpp_merge<0x128, 0x3>(yh[i], xh[i]);
+      } else {
+        const double recv = xor_lane<H>(u ? xh[i] : yh[i]);
+        w[i] = u ? recv : xh[i];
+        w[H + i] = u ? yh[i] : recv;
+      }
     }
     if constexpr (NP == 16) {
       // NP = 16: the column stays where the sweeps left it and stage 2 stores it under the index it carries -- nothing in between
@@ -1313,7 +1403,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       const double tq = dot_bcast16(txd, ya) * k2;  // lane e: k_e^2 (Y^T v0)_e
 #pragma unroll
       for (int i = 0; i < NP; ++i) x[i] = ya[i] * tq;
-      const double qv = transpose_reduce<NP>(x, j);  // Qm v0 = Y k^2 Y^T v0 (exact for the rotated columns)
+      const double qv = transpose_reduce<NP, kDppMerge>(x, j);  // Qm v0 = Y k^2 Y^T v0 (exact for the rotated columns)
       const double rmu0 = fast_rcp(mu0);
       const double rhat = 2.0 * T_j * xo * invmu_j * rmu0 - qv;
       double lc[NP];  // column j of L (zero above the diagonal)
@@ -1323,8 +1413,8 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       const double h = dot_bcast16(g, zc) * fast_rcp(rmu0 * rmu0 - k2);  // h = Z^T g / (1/mu0^2 - k^2)
 #pragma unroll
       for (int i = 0; i < NP; ++i) x[i] = ya[i] * h;
-      sh = transpose_reduce<NP>(x, j);     // shat = L^-T Z h = Y h
-      const double e = dot_bcast16(sh, lc);  // t = L^T shat
+      sh = transpose_reduce<NP, kDppMerge>(x, j);  // shat = L^-T Z h = Y h
+      const double e = dot_bcast16(sh, lc);        // t = L^T shat
       double lr[NP];  // row j of L
 #pragma unroll
       for (int r = 0; r < NP; ++r) lr[r] = L_[lix(j, 0) + r];
@@ -1509,8 +1599,8 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
           xu[i] = py - pa;
           xd[i] = py + pa;
         }
-        up = transpose_reduce<NP>(xu, j) * rT;
-        dn = transpose_reduce<NP>(xd, j) * rT;
+        up = transpose_reduce<NP, kDppMerge && NP == 16>(xu, j) * rT;
+        dn = transpose_reduce<NP, kDppMerge && NP == 16>(xd, j) * rT;
       }
       if (valid && act) {
         double* dq = d.dq + (((long)c * d.L + l) * d.Ns + q) * 2 * NP;
