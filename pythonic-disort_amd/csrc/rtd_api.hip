@@ -1050,6 +1050,7 @@ int rtd_plan_set_quadrature(rtd_plan* p, const double* mu_pos, const double* wei
   p->fork_needed = true;
   p->tables_valid = false;
   p->quad_tables_valid = false;
+  p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read the nodes)
   p->solved = false;
   return 0;
 }
@@ -1163,6 +1164,7 @@ int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* 
   p->have_cols = true;
   p->fork_needed = true;
   p->tables_valid = false;
+  p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read taus0, scale and mu0 of the batch)
   p->solved = false;
   return 0;
 }
@@ -1229,6 +1231,7 @@ int rtd_plan_set_columns_raw(rtd_plan* p, const double* tau_arr, const double* o
   p->have_cols = true;
   p->fork_needed = true;
   p->tables_valid = false;
+  p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read taus0, scale and mu0 of the batch)
   p->solved = false;
   return 0;
 }

@@ -40,8 +40,9 @@ import numpy as np
 import mpmath as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "pythonic-disort_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "pythonic-disort_amd"), os.path.join(ROOT, "tools")]
 from oracle import disort_oracle as O  # noqa: E402  (host-side preparation only: delta-M scaling, quadrature, tables)
+import nt_truth  # noqa: E402
 
 mp.mp.dps = 40
 OUT = os.path.join(ROOT, "tests", "golden", "hp")
@@ -321,15 +322,11 @@ def case_synth(key):
 
 def _nt_correction(kw, tau, phi):
     """The Nakajima-Tanaka terms the reference adds to u when NT_cor is on (pydisort.py:375-698): closed forms of the INPUTS
-    (optical depths, phase-function moments, beam), independent of the solved coefficients -- formed in float64 by the oracle
-    as u(NT_cor=True) - u(NT_cor=False) of one and the same solve (the difference cancels to ~1e-16 of u; the ill-conditioning
-    of these cases sits in the eigen-decomposition and the boundary-condition system, which the 40-digit solve replaces)."""
-    kw_on = dict(kw, NT_cor=True)
-    kw_off = dict(kw, NT_cor=False)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        on, off = O.pydisort(**kw_on)[4](tau, phi), O.pydisort(**kw_off)[4](tau, phi)
-    return np.asarray(on) - np.asarray(off)
+    (optical depths, phase-function moments, beam), independent of the solved coefficients -- evaluated in 40 digits by
+    tools/nt_truth.py, which shares no code with oracle/.  (The committed golden_4a / 4b / 5a / 5b fixtures predate it: their NT
+    part is the float64 oracle's u(NT_cor=True) - u(NT_cor=False); tests/test_nt_truth_cpu.py holds that difference against the
+    40-digit terms at the same points.)"""
+    return nt_truth.correction(kw, tau, phi)["value"]
 
 
 def _golden_call(job):
@@ -341,7 +338,8 @@ def _golden_call(job):
 def run_golden(test_id):
     """A reference-captured case (tests/golden/ref/<test_id>.npz): the truth of the FIRST plain `u(tau, phi)` evaluation
     of every captured pydisort call, stored as c<i>.u with the shape the reference returned (squeezed axes); calls made with
-    the Nakajima-Tanaka corrections on get the (input-only, float64) correction terms added: c<i>.nt = 1."""
+    the Nakajima-Tanaka corrections on get the (input-only, 40-digit: tools/nt_truth.py) correction terms added: c<i>.nt = 1 and
+    c<i>.nt_provenance."""
     import goldens
     calls = goldens.load(test_id)
     jobs, meta = [], []
@@ -366,6 +364,7 @@ def run_golden(test_id):
         if nt:
             u = u + np.asarray(_nt_correction(job[0], job[1], job[2])).reshape(shape)
             res[f"c{ci}.nt"] = np.array(1)
+            res[f"c{ci}.nt_provenance"] = np.array(nt_truth.PROVENANCE)
         res[f"c{ci}.u"] = u
         res[f"c{ci}.flux_up"] = fup
         big = np.abs(u) > 1e-8 * np.max(np.abs(u))
