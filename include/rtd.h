@@ -146,6 +146,41 @@ int rtd_plan_set_columns_raw(rtd_plan* plan, const double* tau_arr, const double
                              const double* phi0, const double* b_pos, const double* b_neg, const double* s_poly,
                              const double* bdrf_q, const double* bdrf_q0);
 
+/* Thermal sources from temperatures, integrated on the device.  DISORT describes a thermal problem by TEMPER, BTEMP, TTEMP,
+ * TEMIS and the band WVNMLO ... WVNMHI; the reference turns them into s_poly_coeffs, b_pos and b_neg on the host with
+ * generate_s_poly_coeffs, blackbody_contrib_to_BCs and generate_emissivity_from_BDRF (subroutines.py:413-454, :354-377,
+ * :459-486; SciPy quadrature of the Planck function).  Here one device thread integrates one (temperature, band) in closed
+ * form (csrc/rtd_planck.h: Gauss-Legendre panels of x^3 / (e^x - 1), float64 accurate from the Rayleigh-Jeans end to the Wien
+ * tail); E(T) below is that integral in W / m^2, with the reference's formula and units (subroutines.py:322-350).
+ *
+ * The plan-free form: out[i] = E(T[i]) over wvnmlo[i] ... wvnmhi[i] (cm^-1), i < n; host arrays in, host array out,
+ * synchronous.  T = 0 and wvnmlo = wvnmhi give 0. */
+int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wvnmlo, const double* wvnmhi, double* out);
+
+/* The thermal description of a batch (host arrays):
+ *   temper   [C][L+1]   level temperatures, top first (TEMPER)
+ *   wvnmlo, wvnmhi [C]  the band of each column
+ *   btemp, ttemp [C]    temperatures of the bottom and top boundaries; NULL: that boundary does not emit
+ *   temis    [C]        emissivity of the top boundary; NULL: 1
+ *   emissivity [C][N]   directional emissivity of the surface; NULL: Kirchhoff's law on the zeroth BDRF mode of the plan,
+ *                       1 - 2 sum_j q^0(mu_i, mu_j) mu_j w_j  (1 when nbdrf = 0) */
+typedef struct {
+  const double *temper, *wvnmlo, *wvnmhi, *btemp, *ttemp, *temis, *emissivity;
+} rtd_thermal;
+
+/* rtd_plan_set_columns_raw with the isotropic source formed on the device from `th` instead of given as s_poly; the plan must
+ * have nscoeffs = 2.  Per column: the level emissions E(temper[l]); the source polynomial of layer l = (intercept, slope) of
+ * the line through (tau_{l-1}, E_l), (tau_l, E_{l+1}) in the unscaled optical depth (linear_spline_coefficients,
+ * subroutines.py:381-409), which the device preparation then treats as a user-given s_poly;
+ *   b_pos[c][0][i] += emissivity[c][i] E(btemp[c]),   b_neg[c][0][i] += temis[c] E(ttemp[c])
+ * on top of what the caller passed (NULL = 0).  With emissivity = NULL and nbdrf > 0 the quadrature must have been set, and
+ * bdrf_q must be the final table (not with rtd_plan_set_bdrf_samples, which forms it later).  Everything else as in
+ * rtd_plan_set_columns_raw. */
+int rtd_plan_set_columns_thermal(rtd_plan* plan, const double* tau_arr, const double* omega_arr, const double* leg_all,
+                                 int32_t nleg_all, const double* f_arr, const double* mu0, const double* I0,
+                                 const double* phi0, const double* b_pos, const double* b_neg, const double* bdrf_q,
+                                 const double* bdrf_q0, const rtd_thermal* th);
+
 /* BDRF Fourier modes formed on the device.  The reference takes the surface as callables
  * BDRF_Fourier_modes[m](mu, -mu') evaluated on the quadrature grid (_solve_for_coeffs.py:121-134); for a reflectance
  * rho(mu, mu', dphi) its tests integrate every mode on the host (pydisotest/6_test.py:194-201).  Here the caller passes

@@ -17,6 +17,7 @@
 #include "../../include/rtd.h"
 #include "rtd_device.h"
 #include "rtd_dd.h"
+#include "rtd_planck.h"
 
 namespace {
 
@@ -1169,14 +1170,110 @@ int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* 
   return 0;
 }
 
-int rtd_plan_set_columns_raw(rtd_plan* p, const double* tau_arr, const double* omega_arr, const double* leg_all,
-                             int32_t nleg_all, const double* f_arr, const double* mu0, const double* I0,
-                             const double* phi0, const double* b_pos, const double* b_neg, const double* s_poly,
-                             const double* bdrf_q, const double* bdrf_q0) {
+namespace {
+
+// Thermal sources from temperatures (include/rtd.h: rtd_thermal; the reference's host helpers generate_s_poly_coeffs,
+// blackbody_contrib_to_BCs, generate_emissivity_from_BDRF: subroutines.py:413-454, :354-377, :459-486).  The math is
+// csrc/rtd_planck.h; one thread per integral, no LDS, no barrier, no cross-lane operation -- the stage moves a few bytes per
+// integral of ~300 exponentials and is nowhere near a limit of the device.
+struct RtdThermalDev {
+  const double *temper, *lo, *hi, *btemp, *ttemp, *temis, *emis;  // the caller's arrays (staged), NULL as there
+  const double* tau;                                              // [C][L] unscaled lower boundaries (staged)
+  double *E;                                                      // [C][L + 3]: the L + 1 levels, then bottom and top boundary
+  double *spoly, *bpos, *bneg;                                    // the raw arrays the preparation kernel reads
+};
+
+__global__ void rtd_planck_band_kernel(long n, const double* T, const double* lo, const double* hi, double* out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = rtd_planck_band(T[i], lo[i], hi[i]);
+}
+
+__global__ void rtd_thermal_emission_kernel(RtdDev d, RtdThermalDev t) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;  // (c, k): k <= L a level, L + 1 the bottom, L + 2 the top boundary
+  const int K = d.L + 3;
+  if (idx >= (long)d.C * K) return;
+  const long c = idx / K;
+  const int k = (int)(idx % K);
+  const double T = k <= d.L ? t.temper[c * (d.L + 1) + k] : k == d.L + 1 ? (t.btemp ? t.btemp[c] : 0.0) : (t.ttemp ? t.ttemp[c] : 0.0);
+  t.E[idx] = rtd_planck_band(T, t.lo[c], t.hi[c]);
+}
+
+__global__ void rtd_thermal_sources_kernel(RtdDev d, RtdThermalDev t) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= d.C) return;
+  const int L = d.L, M = d.M, N = d.N, NP = d.NP, NB = d.NBDRF;
+  const double* E = t.E + c * (L + 3);
+  // linear_spline_coefficients (subroutines.py:381-409) through (0, tau_0, ..., tau_{L-1}) x (E_0 ... E_L): (intercept, slope)
+  double top = 0.0;
+  for (int l = 0; l < L; ++l) {
+    const double bot = t.tau[c * L + l], slope = (E[l + 1] - E[l]) / (bot - top);
+    t.spoly[(c * L + l) * 2] = E[l] - slope * top;
+    t.spoly[(c * L + l) * 2 + 1] = slope;
+    top = bot;
+  }
+  if (t.btemp) {  // b_pos of mode 0 += emissivity x blackbody emission of the surface (pydisotest/9_test.py:196-197)
+    const double* q = NB > 0 ? d.bdrfq + c * NB * NP * NP : nullptr;  // the zeroth mode, rows padded to NP
+    for (int i = 0; i < N; ++i) {
+      double em = 1.0;
+      if (t.emis) {
+        em = t.emis[c * N + i];
+      } else if (q) {  // Kirchhoff: 1 - 2 sum_j q^0(mu_i, mu_j) mu_j w_j over the N real nodes
+        double s = 0.0;
+        for (int j = 0; j < N; ++j) s += q[i * NP + j] * d.mu[j] * d.w[j];
+        em = 1.0 - 2.0 * s;
+      }
+      t.bpos[c * M * N + i] += em * E[L + 1];
+    }
+  }
+  if (t.ttemp) {  // b_neg of mode 0 += TEMIS x blackbody emission of the top boundary (:198-199)
+    const double v = (t.temis ? t.temis[c] : 1.0) * E[L + 2];
+    for (int i = 0; i < N; ++i) t.bneg[c * M * N + i] += v;
+  }
+}
+
+}  // namespace
+
+int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wvnmlo, const double* wvnmhi, double* out) {
+  if (n < 0 || (n > 0 && (!T || !wvnmlo || !wvnmhi || !out))) return fail(RTD_ERR_ARG, "planck_band: null argument or n < 0");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(device));
+  void* buf_v = nullptr;
+  size_t got = 0;
+  HIP_TRY(pooled_malloc(&buf_v, (size_t)n * 4 * 8, device, &got));
+  double* buf = (double*)buf_v;
+  const size_t nb = (size_t)n * 8;
+  hipError_t e = hipMemcpy(buf, T, nb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(buf + n, wvnmlo, nb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(buf + 2 * n, wvnmhi, nb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(rtd_planck_band_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)0, (long)n, buf,
+                       buf + n, buf + 2 * n, buf + 3 * n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, buf + 3 * n, nb, hipMemcpyDeviceToHost);  // (waits for the kernel)
+  else (void)hipStreamSynchronize((hipStream_t)0);
+  pooled_free(buf, got, device);
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("planck_band: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// rtd_plan_set_columns_raw (th == nullptr: exactly its copies and launches) and rtd_plan_set_columns_thermal (s_poly == nullptr,
+// the source polynomials and the boundary emissions are formed in the staging block before the preparation kernel reads it)
+static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double* omega_arr, const double* leg_all,
+                                int32_t nleg_all, const double* f_arr, const double* mu0, const double* I0,
+                                const double* phi0, const double* b_pos, const double* b_neg, const double* s_poly,
+                                const double* bdrf_q, const double* bdrf_q0, const rtd_thermal* th) {
   if (!p || !tau_arr || !omega_arr || !leg_all || !f_arr || !mu0 || !I0 || !phi0) return fail(RTD_ERR_ARG, "null argument");
   const RtdDev& d = p->d;
   if (nleg_all < d.P) return fail(RTD_ERR_ARG, "nleg_all must be >= nleg");
-  if (d.Ns > 0 && !s_poly) return fail(RTD_ERR_ARG, "s_poly is required when nscoeffs > 0");
+  if (th) {
+    if (d.Ns != 2) return fail(RTD_ERR_ARG, "thermal sources need a plan with nscoeffs = 2");
+    if (!th->temper || !th->wvnmlo || !th->wvnmhi) return fail(RTD_ERR_ARG, "thermal: temper, wvnmlo and wvnmhi are required");
+    if (th->btemp && !th->emissivity && d.NBDRF > 0 && !p->have_quad)
+      return fail(RTD_ERR_STATE, "thermal: set_quadrature must precede the Kirchhoff emissivity");
+  } else if (d.Ns > 0 && !s_poly) {
+    return fail(RTD_ERR_ARG, "s_poly is required when nscoeffs > 0");
+  }
   if (d.NBDRF > 0 && (!bdrf_q || !bdrf_q0)) return fail(RTD_ERR_ARG, "BDRF tables are required when nbdrf > 0");
   HIP_TRY(hipSetDevice(p->device));
   const int64_t C = d.C, L = d.L, M = d.M, N = d.N, NP = d.NP, Ns = d.Ns, NB = d.NBDRF;
@@ -1186,7 +1283,11 @@ int rtd_plan_set_columns_raw(rtd_plan* p, const double* tau_arr, const double* o
   hipStream_t s = p->stream;
   // one temporary device block for the raw arrays
   const int64_t n_cl = C * L, n_leg = C * L * nleg_all, n_b = C * M * N, n_sp = C * L * Ns;
-  const int64_t total = 3 * n_cl + n_leg + 3 * C + (b_pos ? n_b : 0) + (b_neg ? n_b : 0) + n_sp;
+  const bool th_bpos = th && th->btemp, th_bneg = th && th->ttemp;  // (the boundary emission is added to b_pos / b_neg, or to zero)
+  const int64_t n_th = !th ? 0
+                           : C * (L + 1) + 2 * C + (th->btemp ? C : 0) + (th->ttemp ? C : 0) + (th->temis ? C : 0) +
+                                 (th->emissivity ? C * N : 0) + C * (L + 3) + (th_bpos && !b_pos ? n_b : 0) + (th_bneg && !b_neg ? n_b : 0);
+  const int64_t total = 3 * n_cl + n_leg + 3 * C + (b_pos ? n_b : 0) + (b_neg ? n_b : 0) + n_sp + n_th;
   // staging block from the process-wide pool (a raw hipMalloc / hipFree pair synchronises the whole device per call)
   void* raw_v = nullptr;
   size_t raw_got = 0;
@@ -1205,7 +1306,29 @@ int rtd_plan_set_columns_raw(rtd_plan* p, const double* tau_arr, const double* o
   up(r.mu0, mu0, C); up(r.I0, I0, C); up(r.phi0, phi0, C);
   if (b_pos) up(r.bpos, b_pos, n_b);
   if (b_neg) up(r.bneg, b_neg, n_b);
-  if (Ns > 0) up(r.spoly, s_poly, n_sp);
+  RtdThermalDev t{};
+  if (th) {
+    auto zero = [&](const double*& dst, int64_t n) {  // an absent b_pos / b_neg that a boundary emission is added to
+      dst = q;
+      if (e == hipSuccess) e = hipMemsetAsync(q, 0, (size_t)n * 8, s);
+      q += n;
+    };
+    if (th_bpos && !b_pos) zero(r.bpos, n_b);
+    if (th_bneg && !b_neg) zero(r.bneg, n_b);
+    r.spoly = q;
+    q += n_sp;
+    up(t.temper, th->temper, C * (L + 1)); up(t.lo, th->wvnmlo, C); up(t.hi, th->wvnmhi, C);
+    if (th->btemp) up(t.btemp, th->btemp, C);
+    if (th->ttemp) up(t.ttemp, th->ttemp, C);
+    if (th->temis) up(t.temis, th->temis, C);
+    if (th->emissivity) up(t.emis, th->emissivity, C * N);
+    t.E = q;
+    q += C * (L + 3);
+    t.tau = r.tau;
+    t.spoly = const_cast<double*>(r.spoly); t.bpos = const_cast<double*>(r.bpos); t.bneg = const_cast<double*>(r.bneg);
+  } else if (Ns > 0) {
+    up(r.spoly, s_poly, n_sp);
+  }
   std::vector<double> qh, q0h;
   if (e == hipSuccess && NB > 0) {  // BDRF tables: padded from N to NP on the host (small)
     qh.assign((size_t)(C * NB * NP * NP), 0.0);
@@ -1217,6 +1340,12 @@ int rtd_plan_set_columns_raw(rtd_plan* p, const double* tau_arr, const double* o
       }
     e = hipMemcpyAsync((void*)d.bdrfq, qh.data(), qh.size() * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync((void*)d.bdrfq0, q0h.data(), q0h.size() * 8, hipMemcpyHostToDevice, s);
+  }
+  if (e == hipSuccess && th) {  // (behind the BDRF tables and the quadrature on the plan's stream: the Kirchhoff sum reads both)
+    const int64_t nE = C * (L + 3);
+    hipLaunchKernelGGL(rtd_thermal_emission_kernel, dim3((unsigned)((nE + 255) / 256)), dim3(256), 0, s, d, t);
+    hipLaunchKernelGGL(rtd_thermal_sources_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, d, t);
+    e = hipGetLastError();
   }
   if (e == hipSuccess) {
     rtd_launch_prepare(d, r, s);
@@ -1234,6 +1363,22 @@ int rtd_plan_set_columns_raw(rtd_plan* p, const double* tau_arr, const double* o
   p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read taus0, scale and mu0 of the batch)
   p->solved = false;
   return 0;
+}
+
+int rtd_plan_set_columns_raw(rtd_plan* p, const double* tau_arr, const double* omega_arr, const double* leg_all,
+                             int32_t nleg_all, const double* f_arr, const double* mu0, const double* I0,
+                             const double* phi0, const double* b_pos, const double* b_neg, const double* s_poly,
+                             const double* bdrf_q, const double* bdrf_q0) {
+  return set_columns_raw_impl(p, tau_arr, omega_arr, leg_all, nleg_all, f_arr, mu0, I0, phi0, b_pos, b_neg, s_poly, bdrf_q, bdrf_q0,
+                              nullptr);
+}
+
+int rtd_plan_set_columns_thermal(rtd_plan* p, const double* tau_arr, const double* omega_arr, const double* leg_all,
+                                 int32_t nleg_all, const double* f_arr, const double* mu0, const double* I0,
+                                 const double* phi0, const double* b_pos, const double* b_neg, const double* bdrf_q,
+                                 const double* bdrf_q0, const rtd_thermal* th) {
+  if (!th) return fail(RTD_ERR_ARG, "thermal: null description");
+  return set_columns_raw_impl(p, tau_arr, omega_arr, leg_all, nleg_all, f_arr, mu0, I0, phi0, b_pos, b_neg, nullptr, bdrf_q, bdrf_q0, th);
 }
 
 int rtd_plan_set_bdrf_samples(rtd_plan* p, int32_t nphi, const double* rho_qq, const double* rho_q0) {

@@ -31,7 +31,9 @@ class Plan:
         self._h = h
         mu, w = _f64(prep["mu"]), _f64(prep["W"])
         _lib.check(lib.rtd_plan_set_quadrature(h, _lib.dptr(mu), _lib.dptr(w)))
-        if prep.get("raw") is not None:
+        if prep.get("raw") is not None and prep.get("thermal") is not None:
+            self.set_columns_thermal(prep["raw"], prep["thermal"])
+        elif prep.get("raw") is not None:
             self.set_columns_raw(prep["raw"])
         else:
             self.set_columns(prep)
@@ -64,7 +66,13 @@ class Plan:
         self.prep = prep
         self.solved = False
 
-    def set_columns_raw(self, raw):
+    def set_columns_thermal(self, raw, thermal):
+        """``set_columns_raw`` with the isotropic source and the boundary emissions formed on the device from temperatures
+        (include/rtd.h: rtd_plan_set_columns_thermal; the plan needs Ns = 2).  raw: as there, without s_poly.  thermal:
+        dict(TEMPER [C, L + 1], WVNMLO, WVNMHI [C], BTEMP, TTEMP, TEMIS [C] or None, emissivity [C, N] or None)."""
+        self.set_columns_raw(raw, thermal)
+
+    def set_columns_raw(self, raw, _thermal=None):
         """Upload a batch as the user gave it; delta-M scaling and source rescaling run on the device
         (include/rtd.h: rtd_plan_set_columns_raw).  raw: dict(tau_arr, omega_arr, f_arr [C, L], leg [C, L, nleg_all],
         mu0, I0, phi0 [C], b_pos / b_neg [C, M, N] or None, s_poly [C, L, Ns] or None, bdrf_q [C, NBDRF, N, N],
@@ -77,7 +85,7 @@ class Plan:
         want = {"tau_arr": (Cn, L), "omega_arr": (Cn, L), "f_arr": (Cn, L), "mu0": (Cn,), "I0": (Cn,), "phi0": (Cn,),
                 "b_pos": (Cn, M, N), "b_neg": (Cn, M, N), "s_poly": (Cn, L, Ns), "bdrf_q": (Cn, NB, N, N),
                 "bdrf_q0": (Cn, NB, N)}
-        required = {"tau_arr", "omega_arr", "f_arr", "mu0", "I0", "phi0"} | ({"s_poly"} if Ns > 0 else set()) \
+        required = {"tau_arr", "omega_arr", "f_arr", "mu0", "I0", "phi0"} | ({"s_poly"} if Ns > 0 and _thermal is None else set()) \
             | ({"bdrf_q", "bdrf_q0"} if NB > 0 else set())
         if a["leg"] is None or a["leg"].ndim != 3 or a["leg"].shape[:2] != (Cn, L) or a["leg"].shape[2] < p["P"]:
             raise ValueError(f"raw batch does not match the plan: leg must be [C = {Cn}, L = {L}, nleg_all >= {p['P']}]")
@@ -93,11 +101,28 @@ class Plan:
                 raise ValueError(f"raw batch does not match the plan: {k} has the shape {a[k].shape}, expected {shape}")
         if not p["beam"] and np.any(a["I0"] > 0):
             raise ValueError("raw batch has a beam source but the plan was created without one")
-        _lib.check(self._lib.rtd_plan_set_columns_raw(
-            self._h, _lib.dptr(a["tau_arr"]), _lib.dptr(a["omega_arr"]), _lib.dptr(a["leg"]), a["leg"].shape[2],
-            *[_lib.dptr(a[k]) for k in ("f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "s_poly", "bdrf_q", "bdrf_q0")]))
+        if _thermal is None:
+            _lib.check(self._lib.rtd_plan_set_columns_raw(
+                self._h, _lib.dptr(a["tau_arr"]), _lib.dptr(a["omega_arr"]), _lib.dptr(a["leg"]), a["leg"].shape[2],
+                *[_lib.dptr(a[k]) for k in ("f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "s_poly", "bdrf_q", "bdrf_q0")]))
+        else:
+            if Ns != 2 or a["s_poly"] is not None:
+                raise ValueError("thermal batch does not match the plan: it needs Ns = 2 and no s_poly")
+            twant = {"TEMPER": (Cn, L + 1), "WVNMLO": (Cn,), "WVNMHI": (Cn,), "BTEMP": (Cn,), "TTEMP": (Cn,), "TEMIS": (Cn,),
+                     "emissivity": (Cn, N)}
+            t = {k: _f64(_thermal.get(k)) for k in twant}
+            for k, shape in twant.items():
+                if t[k] is None:
+                    if k in ("TEMPER", "WVNMLO", "WVNMHI"):
+                        raise ValueError(f"thermal batch does not match the plan: {k} is required")
+                elif t[k].shape != shape:
+                    raise ValueError(f"thermal batch does not match the plan: {k} has the shape {t[k].shape}, expected {shape}")
+            th = _lib.rtd_thermal(*[_lib.dptr(t[k]) for k in ("TEMPER", "WVNMLO", "WVNMHI", "BTEMP", "TTEMP", "TEMIS", "emissivity")])
+            _lib.check(self._lib.rtd_plan_set_columns_thermal(
+                self._h, _lib.dptr(a["tau_arr"]), _lib.dptr(a["omega_arr"]), _lib.dptr(a["leg"]), a["leg"].shape[2],
+                *[_lib.dptr(a[k]) for k in ("f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")], C.byref(th)))
         # what later checks (set_columns, the closures' tau range, beam terms) compare against follows the new batch
-        self.prep = dict(p, tau=a["tau_arr"], mu0=a["mu0"], phi0=a["phi0"], raw=raw)
+        self.prep = dict(p, tau=a["tau_arr"], mu0=a["mu0"], phi0=a["phi0"], raw=raw, thermal=_thermal)
         self.solved = False
 
     def close(self):
@@ -406,6 +431,18 @@ class Plan:
         s = C.c_int32()
         _lib.check(self._lib.rtd_plan_max_sweeps(self._h, C.byref(s)))
         return s.value
+
+
+def planck_band(T, WVNMLO, WVNMHI, device=0):
+    """Planck function integrated over the band WVNMLO ... WVNMHI (cm^-1) at temperature(s) T (K), in W / m^2 -- what the
+    reference's ``blackbody_contrib_to_BCs`` integrates with SciPy on the host, on the device in closed form and for a band per
+    element (include/rtd.h: rtd_planck_band).  The arguments broadcast; the result has the shape of ``T``."""
+    T = np.asarray(T, dtype=np.float64)
+    lo, hi = np.asarray(WVNMLO, dtype=np.float64), np.asarray(WVNMHI, dtype=np.float64)
+    t, lo, hi = (np.ascontiguousarray(np.broadcast_to(a, T.shape)) for a in (T, lo, hi))
+    out = np.empty(T.shape)
+    _lib.check(_lib.load().rtd_planck_band(int(device), out.size, _lib.dptr(t), _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(out)))
+    return out[()]
 
 
 def device_count():

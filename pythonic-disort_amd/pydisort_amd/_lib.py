@@ -26,6 +26,11 @@ class rtd_inputs(C.Structure):
                  "phi0", "rescale", "b_pos", "b_neg", "s_poly", "bdrf_q", "bdrf_q0")]
 
 
+class rtd_thermal(C.Structure):
+    """Thermal description of a batch for rtd_plan_set_columns_thermal (include/rtd.h: rtd_thermal)."""
+    _fields_ = [(n, _dp) for n in ("temper", "wvnmlo", "wvnmhi", "btemp", "ttemp", "temis", "emissivity")]
+
+
 # every symbol include/rtd.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "rtd_version": (C.c_int, []),
@@ -48,6 +53,8 @@ SIGNATURES = {
     "rtd_plan_set_quadrature": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_set_columns": (C.c_int, [_vp] + [_dp] * 14),
     "rtd_plan_set_columns_raw": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 9),
+    "rtd_plan_set_columns_thermal": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8 + [C.POINTER(rtd_thermal)]),
+    "rtd_planck_band": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp]),
     "rtd_plan_set_bdrf_samples": (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     "rtd_plan_set_mode_shard": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "rtd_plan_invalidate_tables": (C.c_int, [_vp]),

@@ -10,6 +10,55 @@ from ._prepare import double_gauss, prepare_columns
 DEFAULT_RETAIN_BYTES = 16 << 30  # pydisort_batch(retain=..., retain_bytes=None): what a call may keep on the device for its evaluators
 
 
+def _thermal_inputs(thermal, C, L, N, with_bdrf_samples):
+    """``pydisort_batch(thermal=...)``: the dict checked and broadcast to what ``Plan.set_columns_thermal`` takes.  Every error a
+    user can make is raised here, before anything touches the device."""
+    known = ("TEMPER", "WVNMLO", "WVNMHI", "BTEMP", "TTEMP", "TEMIS", "emissivity")
+    unknown = set(thermal) - set(known)
+    if unknown:
+        raise ValueError(f"thermal: unknown entries {sorted(unknown)} (known: {', '.join(known)}).")
+    for k in known[:3]:
+        if thermal.get(k) is None:
+            raise ValueError(f"thermal: {k} is required.")
+    T = np.asarray(thermal["TEMPER"], float)
+    if T.ndim not in (1, 2) or T.shape[-1] != L + 1:
+        raise ValueError("Missing temperature specification at some boundaries / interfaces.")
+    if T.ndim == 2 and T.shape[0] != C:
+        raise ValueError("thermal: TEMPER must be [C, L + 1] or [L + 1].")
+
+    def per_column(k):
+        v = thermal.get(k)
+        if v is None:
+            return None
+        v = np.asarray(v, float)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape != (C,)):
+            raise ValueError(f"thermal: {k} must be a scalar or [C].")
+        return np.ascontiguousarray(np.broadcast_to(v, (C,)))
+
+    out = dict(TEMPER=np.ascontiguousarray(np.broadcast_to(T, (C, L + 1))))
+    for k in known[1:6]:
+        out[k] = per_column(k)
+    for k in ("TEMPER", "BTEMP", "TTEMP"):
+        if out[k] is not None and not np.all(out[k] >= 0):
+            raise ValueError(f"thermal: {k} must not be negative.")
+    if not (np.all(out["WVNMLO"] >= 0) and np.all(out["WVNMLO"] <= out["WVNMHI"])):
+        raise ValueError("thermal: need 0 <= WVNMLO <= WVNMHI.")
+    em = thermal.get("emissivity")
+    if em is None:
+        if with_bdrf_samples:
+            raise ValueError("thermal: give `emissivity` with bdrf_samples -- the BDRF modes that Kirchhoff's law would use are "
+                             "formed on the device after the sources.")
+    else:
+        em = np.asarray(em, float)
+        if em.ndim == 0 or em.shape == (C,):
+            em = np.broadcast_to(em.reshape(-1, 1), (C, N))
+        elif em.shape != (C, N):
+            raise ValueError("thermal: emissivity must be a scalar, [C] or [C, N].")
+        em = np.ascontiguousarray(em)
+    out["emissivity"] = em
+    return out
+
+
 class BatchSolution:
     """Evaluators over all columns; arrays carry a leading column axis.
 
@@ -61,7 +110,8 @@ class BatchSolution:
 def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLeg=None, NFourier=None,
                    b_pos=0, b_neg=0, only_flux=False, f_arr=0, NT_cor=False, bdrf_q=None, bdrf_q0=None,
                    s_poly_coeffs=None, device=0, bdrf_samples=None, NBDRF=None, mode_shard=None, work_columns=0,
-                   device_prepare=False, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False):
+                   device_prepare=False, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False,
+                   thermal=None):
     """Like ``pydisort`` with a leading column axis on every atmospheric input:
     tau_arr, omega_arr, f_arr [C, L]; Leg_coeffs_all [C, L, NLeg_all]; mu0, I0, phi0 [C];
     b_pos / b_neg: scalar, [C], [C, N] or [C, N, NFourier]; s_poly_coeffs [C, L, Ns];
@@ -76,6 +126,14 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
     result (u0, fluxes and NT corrections come from shard 0 only; ``Plan.allreduce_results`` sums across RCCL ranks).
     device_prepare=True: the delta-M scaling and the source rescaling of pydisort.py:316-372 run on the device from the raw
     inputs (``rtd_plan_set_columns_raw``) instead of in NumPy -- for throughput batches; not with NT_cor or mode_shard.
+    thermal=dict(TEMPER=..., WVNMLO=..., WVNMHI=..., BTEMP=None, TTEMP=None, TEMIS=1.0, emissivity=None): the thermal problem as
+    DISORT states it -- level temperatures TEMPER [C, L + 1] or [L + 1], the wavenumber band (cm^-1), the temperatures of the bottom
+    and top boundaries and the top's emissivity (scalars or [C]; None: that boundary does not emit).  The device integrates the
+    Planck function per level and boundary and forms what the reference's host helpers ``generate_s_poly_coeffs``,
+    ``blackbody_contrib_to_BCs`` and ``generate_emissivity_from_BDRF`` return: the linear-in-tau source of every layer, and
+    emissivity x E(BTEMP), TEMIS x E(TTEMP) ADDED to b_pos, b_neg (include/rtd.h: rtd_plan_set_columns_thermal).  emissivity: scalar,
+    [C] or [C, N]; None: Kirchhoff's law on the zeroth mode of ``bdrf_q`` (1 without a BDRF; not with ``bdrf_samples``).  Implies
+    device_prepare=True; excludes ``s_poly_coeffs``.
     numeric_errors: "raise" (a column whose solve fails numerically -- e.g. a phase function whose truncation is not
     positive -- raises NumericalError from the evaluators; ``sol.plan.column_status()`` tells which) or "nan" (the failed
     columns are NaN in the returned arrays, every other column keeps its result: one bad column does not cost the batch).
@@ -131,6 +189,12 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
             raise ValueError("The shape of a boundary condition is incorrect.")
         return out
 
+    th = None
+    if thermal is not None:
+        if s_poly_coeffs is not None:
+            raise ValueError("Give either s_poly_coeffs or thermal, not both.")
+        th = _thermal_inputs(thermal, C, L, N, bdrf_samples is not None)
+        device_prepare = True
     f_arr = np.broadcast_to(np.asarray(f_arr, float), (C, L))
     sp = np.zeros((C, L, 0)) if s_poly_coeffs is None or np.all(np.asarray(s_poly_coeffs) == 0) \
         else np.asarray(s_poly_coeffs, float).reshape(C, L, -1)
@@ -153,8 +217,8 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
                    s_poly=sp if sp.shape[2] > 0 else None,
                    bdrf_q=bq if bq.shape[1] > 0 else None, bdrf_q0=bq0 if bq.shape[1] > 0 else None)
         mu, W = double_gauss(N)
-        prep = dict(C=C, L=L, N=N, P=NLeg, M=NFourier, Ns=sp.shape[2], NBDRF=bq.shape[1], beam=bool(np.any(I0 > 0)),
-                    mu=mu, W=W, tau=tau_arr, raw=raw)
+        prep = dict(C=C, L=L, N=N, P=NLeg, M=NFourier, Ns=2 if th is not None else sp.shape[2], NBDRF=bq.shape[1],
+                    beam=bool(np.any(I0 > 0)), mu=mu, W=W, tau=tau_arr, raw=raw, thermal=th)
     else:
         prep = prepare_columns(tau_arr, omega_arr, NQuad, Leg, mu0, I0, phi0, NLeg, NFourier, bc(b_pos), bc(b_neg),
                                f_arr, sp, bq, bq0)

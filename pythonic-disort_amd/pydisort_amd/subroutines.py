@@ -5,6 +5,11 @@ relative to src/PythonicDISORT/subroutines.py) so that scripts written against t
 sources, blackbody boundary terms, emissivities, cached BDRF modes, actinic fluxes, mu-interpolation -- run
 unchanged on top of ``pydisort_amd.pydisort``.  These are input/output conveniences on the host; the solver itself
 runs on the GPU.  Parity with the reference's outputs is pinned by tests/golden/helpers.npz.
+
+The three thermal helpers -- ``generate_s_poly_coeffs``, ``blackbody_contrib_to_BCs``, ``generate_emissivity_from_BDRF`` -- also
+have a device form for batches: ``pydisort_batch(thermal=dict(TEMPER=..., WVNMLO=..., WVNMHI=..., BTEMP=..., TTEMP=..., TEMIS=...))``
+and ``pydisort_amd.planck_band`` (include/rtd.h: rtd_plan_set_columns_thermal, rtd_planck_band), where SciPy's quadrature here
+would cost more than the solve; the host versions below remain what ``pydisort()`` callers use.
 """
 import inspect
 import warnings
