@@ -17,6 +17,7 @@
 // DPP / ds_swizzle cross-lane moves, small vectors and the Cholesky factor go through LDS.
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "rtd_device.h"
 
@@ -108,6 +109,9 @@ __device__ __forceinline__ double approx_rcp(double x) {
 
 #ifndef RTD_JAC_F32_ANGLE
 #define RTD_JAC_F32_ANGLE 1  /* rotation angle of the pair-layout sweeps from float arithmetic (see PairStep) */
+#endif
+#ifndef RTD_JAC_SMALL_ANGLE
+#define RTD_JAC_SMALL_ANGLE 1  /* pair-layout sweeps, NP <= 16: steps in which the whole wavefront has |t| < 2^-27 rotate with c = 1 exactly (see PairStep) */
 #endif
 #ifndef RTD_CHOL_FMAC_DPP
 #define RTD_CHOL_FMAC_DPP 1  /* Cholesky trailing updates as ONE v_fmac_f64_dpp (row_newbcast) per element, NP = 16 */
@@ -654,7 +658,14 @@ template <int NP, int S>
 struct PairStep {
   static constexpr int H = NP / 2;
   static __device__ __forceinline__ void run(double (&xh)[H], double (&yh)[H], double& ax, double& ay, int& ix, int& iy,
-                                             const int p, int& notconv) {
+                                             const int p, unsigned long long& notconv) {
+    step(xh, yh, ax, ay, ix, iy, p, notconv, std::make_integer_sequence<int, H>{});
+    PairStep<NP, S + 1>::run(xh, yh, ax, ay, ix, iy, p, notconv);
+  }
+  // I...: 0 ... H - 1, the element indices of the rotation as constants of the source (see the small-angle step below)
+  template <int... I>
+  static __device__ __forceinline__ void step(double (&xh)[H], double (&yh)[H], double& ax, double& ay, int& ix, int& iy,
+                                              const int p, unsigned long long& notconv, std::integer_sequence<int, I...>) {
     constexpr JSched<NP> sched{};
     constexpr int SW = sched.sw[S], MK = sched.mk[S];
     double g0 = 0.0, g1 = 0.0;
@@ -679,49 +690,73 @@ struct PairStep {
     const float r2f = fmaf(df, df, fmaf(gf, gf, 1e-36f));
     const float rhof = r2f * __builtin_amdgcn_rsqf(r2f);
     const float denf = df + copysignf(rhof, df);
-    const double tt = (double)(gf * __builtin_amdgcn_rcpf(denf));
+    const float tf = gf * __builtin_amdgcn_rcpf(denf);
+    const double tt = (double)tf;
 #else
     const double r2 = fma(delta, delta, fma(g2, g2, 1e-280));
     const double rho = r2 * approx_rsqrt(r2);
     const double den = delta + copysign(rho, delta);
     const double tt = g2 * approx_rcp(den);
+    const float tf = (float)tt;
 #endif
-    // c from ONE Newton step (4e-15): the error scales BOTH columns of the pair by the same 1 + eps, so orthogonality and
-    // the directions z are untouched; only the norms k drift, by ~50 rotations x 4e-15 (parity unchanged)
-    const double c = approx_rsqrt(fma(tt, tt, 1.0));
-    const double sn = tt * c;
-    notconv |= (gamma * gamma > RTD_JAC_TOL * ax * ay) ? 1 : 0;
+    // the stop test as a lane mask, accumulated on the scalar unit: only "any lane, any step" is ever asked.  (The per-lane flag
+    // was that already in the straight-line sweep; between the branches of the small-angle steps the compiler moved all 15
+    // compares, with the gamma, ax and ay they read, to the end of the sweep: 90 registers held for nothing.)
+    notconv |= __builtin_amdgcn_ballot_w64(gamma * gamma > RTD_JAC_TOL * ax * ay);
     const double nax = fma(-tt, gamma, ax), nay = fma(tt, gamma, ay);  // |c x - s y|^2, |s x + c y|^2
-    // (x, y) <- (c x - s y, s x + c y), written the other way round in the slots that hand on their x
-    double cxx = c, cxy = -sn, cyx = sn, cyy = c;
+    // Small-angle step: below |t| = 2^-27, fma(t, t, 1.0) rounds to 1.0, so c is the number 1 and s is t -- the last sweep of a
+    // wavefront and part of the one before consist of such steps (tools/jacobi_small_angle.py counts them).  ONE decision for the
+    // whole wavefront (a lane mask tested on the scalar unit; a NaN counts as large): when every pair is below the bound, the
+    // rsq + Newton chain is skipped and the steps that hand on Y everywhere rotate as x - t y, y + t x, without the products
+    // by 1.  The same bits as the general form whenever the hardware's rsq(1.0) is 1.0; one rounding of c otherwise.
+    const bool small = RTD_JAC_SMALL_ANGLE != 0 && __builtin_amdgcn_ballot_w64(!(fabsf(tf) < 0x1p-27f)) == 0;
+    // The two forms meet in xn, yn, arrays of the step's own whose every index is a constant of the source (pack expansions, not
+    // loops): those become scalars before anything is inlined or unrolled.  Written into xh, yh inside the branches -- or into
+    // local arrays indexed by loops -- the forms met in whole columns, register tuples of 2 H dwords each, copied at the join.
+    // Each form moves its Y on itself (the DPP move writes where the join expects the column: with the moves behind the join
+    // the small-angle form paid H register copies for the H multiplications it saved).
+    double xn[H], yn[H];
+    if (SW == 0 && small) {
+      ((xn[I] = fma(-tt, yh[I], xh[I]), yn[I] = xor_lane<MK>(fma(tt, xh[I], yh[I]))), ...);
+    } else {
+      double c = 1.0, sn = tt;
+      if (!small) {
+        // c from ONE Newton step (4e-15): the error scales BOTH columns of the pair by the same 1 + eps, so orthogonality and
+        // the directions z are untouched; only the norms k drift, by ~50 rotations x 4e-15 (parity unchanged)
+        c = approx_rsqrt(fma(tt, tt, 1.0));
+        sn = tt * c;
+      }
+      // (x, y) <- (c x - s y, s x + c y), written the other way round in the slots that hand on their x
+      double cxx = c, cxy = -sn, cyx = sn, cyy = c;
+      if constexpr (SW != 0) {
+        const bool swp = (p & SW) != 0;
+        cxx = swp ? sn : c;
+        cxy = swp ? c : -sn;
+        cyx = swp ? c : sn;
+        cyy = swp ? -sn : c;
+      }
+      ((xn[I] = fma(cxy, yh[I], cxx * xh[I]), yn[I] = xor_lane<MK>(fma(cyy, yh[I], cyx * xh[I]))), ...);
+    }
+    // both forms rejoin here: the norm and the index of the column that moved on
     double oax = nax, oay = nay;
     if constexpr (SW != 0) {
       const bool swp = (p & SW) != 0;
-      cxx = swp ? sn : c;
-      cxy = swp ? c : -sn;
-      cyx = swp ? c : sn;
-      cyy = swp ? -sn : c;
       oax = swp ? nay : nax;
       oay = swp ? nax : nay;
       const int t = swp ? iy : ix;
       iy = swp ? ix : iy;
       ix = t;
     }
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-      const double xi = xh[i], yi = yh[i];
-      xh[i] = fma(cxy, yi, cxx * xi);
-      yh[i] = xor_lane<MK>(fma(cyy, yi, cyx * xi));
-    }
+    ((xh[I] = xn[I], yh[I] = yn[I]), ...);
     ax = oax;
     ay = xor_lane<MK>(oay);
     iy = xor_lane_i<MK>(iy);
-    PairStep<NP, S + 1>::run(xh, yh, ax, ay, ix, iy, p, notconv);
   }
 };
 template <int NP>
 struct PairStep<NP, NP - 1> {  // the last step of a sweep is step NP - 2
-  static __device__ __forceinline__ void run(double (&)[NP / 2], double (&)[NP / 2], double&, double&, int&, int&, const int, int&) {}
+  static __device__ __forceinline__ void run(double (&)[NP / 2], double (&)[NP / 2], double&, double&, int&, int&, const int,
+                                             unsigned long long&) {}
 };
 
 #ifndef RTD_JAC_FAST
@@ -1229,7 +1264,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     }
     int ix = p, iy = p + H;  // the columns' starting indices travel with them
     for (int sweep = 0; sweep < 40; ++sweep) {
-      int notconv = 0;
+      bool done;
       double ax = 0.0, ay = 0.0;
 #pragma unroll
       for (int i = 0; i < H; ++i) {
@@ -1239,6 +1274,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       ax += xor_lane<H>(ax);
       ay += xor_lane<H>(ay);
       if constexpr (RTD_JAC_FAST && NP >= 32) {
+        int notconv = 0;
         double sx = 1.0, sy = 1.0, rx = 1.0, ry = 1.0;
         FastPairStep<NP, 0>::run(xh, yh, ax, ay, ix, iy, p, notconv, sx, sy, rx, ry);
 #pragma unroll
@@ -1246,11 +1282,14 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
           xh[i] *= sx;
           yh[i] *= sy;
         }
+        done = !__any(notconv);
       } else {
+        unsigned long long notconv = 0;  // lanes that met a pair above the tolerance
         PairStep<NP, 0>::run(xh, yh, ax, ay, ix, iy, p, notconv);
+        done = notconv == 0;
       }
       ++nsweep;
-      if (!__any(notconv)) {
+      if (done) {
         converged = true;
         break;
       }
