@@ -21,13 +21,15 @@ three parties.  Nakajima-Tanaka corrections are post-processing and are left out
 
 Fixtures: tests/golden/hp/<family>_<seed>.npz = the evaluation points, u [Q, ntau, nphi], u0, flux_up of the truth and,
 for the record, the oracle's distance to it.  Families: random32 / random64 / random (the seeded generators of
-tests/test_gpu_random_parity.py) and golden (a reference-captured case of tests/golden/ref by name).
+tests/test_gpu_random_parity.py), golden (a reference-captured case of tests/golden/ref by name) and phase (a column of
+tests/phase_cases.py, "<NQuad>_<column>": phase functions beyond Henyey-Greenstein; these fixtures also carry both parts of flux_down).
 
 Usage (build container; minutes per case on 6 processes):
     python3 tools/hp_truth_case.py random32 9 25          # family, seeds ...
     python3 tools/hp_truth_case.py random64 11
     python3 tools/hp_truth_case.py golden 8ARTS_A
     python3 tools/hp_truth_case.py synth cfg4_9 cfg5_0     # a column of a synthetic BASELINE config (cfg5: ~1.5 h)
+    python3 tools/hp_truth_case.py phase 30_c3 62_c5      # columns of tests/phase_cases.py; "phase all": every one (~7 min on 8 processes)
     python3 tools/hp_truth_case.py --near-conservative    # every random32 / random64 seed with an omega > 1 - 1e-5 layer
 """
 import multiprocessing
@@ -263,9 +265,8 @@ def solve_mode(args):
     return out
 
 
-def truth(kw, tau, phi, parallel=True):
-    """(u [Q, ntau, nphi] or None when only_flux, u0 [Q, ntau], flux_up [ntau]) of the 40-digit solution at optical depths
-    tau and azimuths phi, in the units of the inputs.  parallel: one process per Fourier mode."""
+def _mode_jobs(kw, tau):
+    """(prepared inputs, one solve_mode job per Fourier mode) of a case at the optical depths tau."""
     kw = dict(kw)
     kw.pop("NT_cor", None)
     with warnings.catch_warnings():
@@ -274,12 +275,10 @@ def truth(kw, tau, phi, parallel=True):
     if not p["beam"]:
         p["mu0"] = 1.0  # no beam: every beam term carries the factor I0 = 0
     _, l_pts, ts_pts = O.Solution._locate(type("S", (), {"p": p})(), tau)
-    jobs = [(p, m, ts_pts, l_pts) for m in range(p["M"])]
-    if parallel and p["M"] > 1:
-        with multiprocessing.Pool(min(WORKERS, p["M"])) as pool:
-            um = pool.map(solve_mode, jobs, chunksize=1)
-    else:
-        um = [solve_mode(j) for j in jobs]
+    return p, [(p, m, ts_pts, l_pts) for m in range(p["M"])]
+
+
+def _from_modes(p, um, phi):
     um = np.stack(um)  # [M, Q, ntau]
     u0 = p["rescale"] * um[0]
     fup = p["rescale"] * 2 * np.pi * (p["mu"] * p["W"]) @ um[0][:p["N"]]
@@ -287,6 +286,35 @@ def truth(kw, tau, phi, parallel=True):
         return None, u0, fup
     cosm = np.cos(np.arange(p["M"])[:, None] * (p["phi0"] - np.atleast_1d(np.asarray(phi, float)))[None, :])
     return p["rescale"] * np.einsum("mit,mp->itp", um, cosm), u0, fup
+
+
+def truth(kw, tau, phi, parallel=True):
+    """(u [Q, ntau, nphi] or None when only_flux, u0 [Q, ntau], flux_up [ntau]) of the 40-digit solution at optical depths
+    tau and azimuths phi, in the units of the inputs.  parallel: one process per Fourier mode."""
+    p, jobs = _mode_jobs(kw, tau)
+    if parallel and p["M"] > 1:
+        with multiprocessing.Pool(min(WORKERS, p["M"])) as pool:
+            um = pool.map(solve_mode, jobs, chunksize=1)
+    else:
+        um = [solve_mode(j) for j in jobs]
+    return _from_modes(p, um, phi)
+
+
+def flux_down_of(kw, tau, u0):
+    """(diffuse, direct) of flux_down from the truth's u0 as the reference forms them (_assemble_intensity_and_fluxes.py:568-601):
+    the quadrature sum over the downward streams plus the delta-scaled direct beam minus the unscaled one, and the unscaled direct
+    beam in closed form.  Sums of positive terms and two exponentials: benign in float64."""
+    kw = dict(kw)
+    kw.pop("NT_cor", None)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        p = O.prepare(**kw)
+    tau, l_pts, ts_pts = O.Solution._locate(type("S", (), {"p": p})(), tau)
+    direct = direct_s = np.zeros(len(tau))
+    if p["beam"]:
+        direct = p["rescale"] * p["I0"] * p["mu0"] * np.exp(-tau / p["mu0"])
+        direct_s = p["rescale"] * p["I0"] * p["mu0"] * np.exp(-ts_pts / p["mu0"])
+    return 2 * np.pi * (p["mu"] * p["W"]) @ u0[p["N"]:] + direct_s - direct, direct
 
 
 def case_of(family, key):
@@ -378,10 +406,14 @@ def run_golden(test_id):
           f"{worst_scale:.2e} of the scale, {worst:.2e} pointwise", flush=True)
 
 
-def run(family, key):
-    kw, tau, phi = case_synth(key) if family == "synth" else case_of(family, key)
-    t0 = time.time()
-    u, u0, fup = truth(kw, tau, phi)
+def case_phase(key):
+    """A column of tests/phase_cases.py, "<NQuad>_<column>", at its own points."""
+    import phase_cases
+    kw = phase_cases.case(key)
+    return (kw,) + tuple(phase_cases.points(kw))
+
+
+def _record(family, key, kw, tau, phi, u, u0, fup, seconds):
     kwo = dict(kw)
     kwo.pop("NT_cor", None)
     with warnings.catch_warnings():
@@ -393,10 +425,35 @@ def run(family, key):
         res.update(u=u, oracle_u_scale_rel=np.max(np.abs(ou - u)) / np.max(np.abs(u)))
         big = np.abs(u) > 1e-8 * np.max(np.abs(u))
         res["oracle_u_pointwise_rel"] = np.max(np.abs(ou - u)[big] / np.abs(u)[big])
+    if family == "phase":
+        res["flux_down_diffuse"], res["flux_down_direct"] = flux_down_of(kw, tau, u0)
     os.makedirs(OUT, exist_ok=True)
     np.savez_compressed(os.path.join(OUT, f"{family}_{key}.npz"), **res)
-    print(f"{family}/{key}: NQuad {kw['NQuad']}, {len(np.atleast_1d(kw['tau_arr']))} layers, {time.time() - t0:.0f} s; oracle vs truth: "
+    print(f"{family}/{key}: NQuad {kw['NQuad']}, {len(np.atleast_1d(kw['tau_arr']))} layers, {seconds:.0f} s; oracle vs truth: "
           + ", ".join(f"{k[7:]} {float(v):.2e}" for k, v in res.items() if k.startswith("oracle_")), flush=True)
+
+
+def run(family, key):
+    kw, tau, phi = case_synth(key) if family == "synth" else case_of(family, key)
+    t0 = time.time()
+    u, u0, fup = truth(kw, tau, phi)
+    _record(family, key, kw, tau, phi, u, u0, fup, time.time() - t0)
+
+
+def run_phase(keys):
+    """The cases of tests/phase_cases.py: the Fourier modes of ALL of them through one pool, the largest first (a case has three
+    modes only, so case by case the workers would idle)."""
+    t0 = time.time()
+    cases = {key: case_phase(key) for key in keys}
+    prepared = {key: _mode_jobs(kw, tau) for key, (kw, tau, phi) in cases.items()}
+    order = sorted(keys, key=lambda k: -cases[k][0]["NQuad"])
+    flat = [(key, job) for key in order for job in prepared[key][1]]
+    with multiprocessing.Pool(WORKERS) as pool:
+        ums = pool.map(solve_mode, [job for _, job in flat], chunksize=1)
+    for key in order:
+        kw, tau, phi = cases[key]
+        u, u0, fup = _from_modes(prepared[key][0], [um for (k, _), um in zip(flat, ums) if k == key], phi)
+        _record("phase", key, kw, tau, phi, u, u0, fup, time.time() - t0)
 
 
 def near_conservative_seeds():
@@ -417,10 +474,18 @@ if __name__ == "__main__":
             sys.exit(0)
     else:
         todo = [(sys.argv[1], k) for k in sys.argv[2:] if not k.startswith("--")]
+    if ("phase", "all") in todo:
+        import phase_cases
+        todo = [t for t in todo if t != ("phase", "all")] + [("phase", k) for k in phase_cases.keys() + [phase_cases.NEGATIVE]]
+    if "--skip-existing" in sys.argv:
+        todo = [(f, k) for f, k in todo if f == "golden" or not os.path.exists(os.path.join(OUT, f"{f}_{k}.npz"))]
+    phase = [k for f, k in todo if f == "phase"]
+    if phase:
+        run_phase(phase)
     for family, key in todo:
+        if family == "phase":
+            continue
         if family == "golden":
             run_golden(key)
-            continue
-        if "--skip-existing" in sys.argv and os.path.exists(os.path.join(OUT, f"{family}_{key}.npz")):
             continue
         run(family, key)
