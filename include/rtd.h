@@ -294,7 +294,7 @@ int rtd_plan_enable_timing(rtd_plan* plan, int32_t enable);
 /* accumulated milliseconds per kernel slot since the last reset (slot names as returned by the Python wrapper):
  * [0] "tables" Legendre tables; [2] "jacobi" the fused rtd_eigen_kernel; [1] "asm" and [3] "post" are the empty slots of
  * the earlier three-kernel eigen stage; [4] "iface" rtd_iface_kernel -- or, at 64 streams, the tiled fused
- * rtd_bc_tile_kernel; [5] "sweep" rtd_sweep_kernel -- or the fused rtd_bc_mfma_kernel when 16 < NQuad <= 32 (slot 4 is
+ * rtd_bc_tile2_kernel; [5] "sweep" rtd_sweep_kernel -- or the fused rtd_bc_mfma_kernel when 16 < NQuad <= 32 (slot 4 is
  * then empty) -- or, at 64 streams, the pivoted kernels' pass over the chains the tiled kernel flagged; [6] "eval"
  * rtd_eval_kernel or, with the fused interface evaluation, rtd_fourier_kernel, plus the NT corrections.  Launches counted in nlaunch[7] (one per window of columns).  Synchronises; with timing
  * enabled every window starts with a stream synchronisation: a measurement mode, not the throughput path. */
@@ -373,8 +373,8 @@ enum {
 
 /* --- environment read by the library (the complete list; tests/test_host_logic.py greps the sources against it) ---------
  * None of these changes a result beyond rounding: they select between implementations that the test suite holds to the same
- * parity (tests/test_gpu_parity.py runs the suite under each), size buffers, or print diagnostics.  Timing experiments whose
- * results are NOT valid (e.g. the aliased hand-off reads of DESIGN.md section 7a) exist only behind compile-time -D flags.
+ * parity (tests/test_gpu_parity.py runs the suite under each), size buffers, or print diagnostics.  A timing experiment whose
+ * results are NOT valid (such as round 3's aliased hand-off reads, HISTORY.md section 7a) is never an environment switch.
  *   RTD_WORK_BYTES        bytes of solve intermediates per plan (default 24 GiB): sizes the automatic column window
  *   RTD_POOL_BYTES        bytes of device memory (per device) of destroyed plans kept for the next plan in blocks above 64 MB
  *                         (default 0: large blocks go straight back to the runtime); the same as rtd_pool_set_limit
@@ -383,14 +383,9 @@ enum {
  *                         path of a failed speculation); =2 every chain of the 32-stream kernel takes the register-resident
  *                         column-pivoted elimination throughout (the path of near-conservative mode-0 chains)
  *   RTD_BC_FORCE_HANDOVER tiled (64-stream) kernel: every third chain goes to the pivoted row-per-lane kernels
- *   RTD_BC_TILED          32 streams through the tiled kernel's T = 1 instance instead of rtd_bc_mfma_kernel
- *   RTD_BC_TILE_V1        64 streams through rtd_bc_tile_kernel<2> (one wavefront per SIMD, rounds 2-3) instead of the lean
- *                         two-wavefronts-per-SIMD kernel of rtd_bc_tile2.hip (round 4)
  *   RTD_BC_WIDE_V1        66 ... 128 streams through the row-per-lane kernels (one wavefront per chain, rounds 1-3) instead of the
  *                         four-wavefronts-per-chain kernels of rtd_bc_wide.hip (round 4)
  *   RTD_EIG_MFMA          eigen stage with its assembly GEMMs on the matrix cores (measured slower; a tested variant)
- *   RTD_EIG_SMALL_V1      2 ... 8 streams: eigen stage through the four-lanes-per-problem instance of the general eigen kernel
- *                         instead of the one-lane-per-problem kernel of rtd_eig_small.hip
  *   RTD_SMALL_SPLIT       2 ... 16 streams through the separate interface / sweep / evaluation kernels instead of the fused
  *                         rtd_bc_small_kernel
  *   RTD_RCCL_STUB         TESTS ONLY: path of a stand-in for the RCCL entry points (tests/stub/librccl_stub.so) for rank processes

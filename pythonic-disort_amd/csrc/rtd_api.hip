@@ -1789,7 +1789,7 @@ int rtd_plan_get_timing(rtd_plan* p, double ms[7], int64_t nlaunch[7], int32_t r
 int rtd_plan_pivoted_chains(rtd_plan* p, int32_t* chains) {
   if (!p || !chains) return fail(RTD_ERR_ARG, "null argument");
   *chains = 0;
-  if (p->d.NP != 32 && !getenv("RTD_BC_TILED")) return 0;
+  if (p->d.NP != 32) return 0;
   const size_t n = (size_t)p->Cw * p->d.M;
   std::vector<int> h(n);
   HIP_TRY(hipMemcpyAsync(h.data(), p->d.need_split, n * sizeof(int), hipMemcpyDeviceToHost, p->stream));

@@ -18,13 +18,15 @@
 //   banded matrix to <= 5e-13 on every golden case and on thick/thin/near-conservative stress cases
 //   (tools/proto_device_algo.py: check_structured).
 //
-// Three implementations.  16 < NQuad <= 32: rtd_bc_mfma_kernel, one wavefront per (column, mode), everything in the
-// matrix-core register layout (see its comment below).  32 < NQuad <= 64: rtd_bc_tile_kernel<2>, the same on 2 x 2 tiles.
-// NQuad <= 16 (and the tiled kernel's last resort for a singular carry block): rtd_iface_kernel (all (column, mode,
+// Two implementations live in this file.  16 < NQuad <= 32: rtd_bc_mfma_kernel, one wavefront per (column, mode), everything in
+// the matrix-core register layout (see its comment below).  The row-per-lane pair: rtd_iface_kernel (all (column, mode,
 // interface) in parallel: Wp, Wq, rho through HBM) and rtd_sweep_kernel (per (column, mode): forward carry recursion,
 // bottom boundary, backward sweep); NP lanes per problem, 64/NP problems per wavefront, lane i owns row i of the carry
-// system.  (An MFMA form of the interface kernel at NP = 16 and a three-wavefront form of rtd_bc_mfma_kernel lost every
-// A/B of round 2 and were removed in round 3.)
+// system, partial pivoting.  It is the last resort of the 64-stream kernel for a singular carry block (NP = 32, flagged chains
+// only) and, at NP = 4, 8 and 64, what RTD_SMALL_SPLIT / RTD_BC_WIDE_V1 select instead of the fused kernels.
+// The other stream counts have files of their own, all on this recursion: NQuad <= 16 rtd_bc_small.hip, 32 < NQuad <= 64
+// rtd_bc_tile2.hip (rtd_bc_mfma_kernel's scheme on 2 x 2 tiles), 64 < NQuad <= 128 rtd_bc_wide.hip; rtd_launch_bc at the end
+// of this file chooses.  (Kernels that lost their A/B runs and were removed: HISTORY.md.)
 #include <cstdlib>
 #include <type_traits>
 
@@ -660,26 +662,14 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
   const long cm = chain_of_block(blockIdx.x, d.C, d.M);
   const int m = (int)(cm % d.M), c = (int)(cm / d.M);
   const int L = d.L, Lm1 = L - 1;
-#ifdef RTD_BC_ALIAS_EXPERIMENT
-  // Timing experiment of a PROFILING build only (-DRTD_BC_ALIAS_EXPERIMENT=1 | 2 | 3 through RTD_EXTRA_FLAGS; results are
-  // garbage; never part of the shipped library: tests/test_host_logic.py checks that no result-changing switch is read from
-  // the environment): the chains read the eigen stage's hand-off of only 32 chains (bit 0: 2.6 MB, served by the L2s) or of
-  // 2 048 chains (bit 1: 168 MB, served by the Infinity Cache); with both bits the factors H, s, rho_b of the forward sweep
-  // are aliased to 32 chains as well.  What the kernel takes then is the floor that any scheme for cutting its HBM traffic
-  // can approach (profiles/archive/r03_experiments.json: bc_traffic_floor).
-  const long cmr = (RTD_BC_ALIAS_EXPERIMENT & 1) ? cm % 32 : (RTD_BC_ALIAS_EXPERIMENT & 2) ? cm % 2048 : cm;
-  const long cmw = ((RTD_BC_ALIAS_EXPERIMENT & 3) == 3) ? cm % 32 : cm;
-#else
-  const long cmr = cm, cmw = cm;
-#endif
-  const double* Ym = d.Ym + cmr * L * NN;
-  const double* Am = d.Am + cmr * L * NN;
-  const double* kk = d.kk + cmr * L * NP;
-  const double* Ek = d.Ek + cmr * L * NP;
-  const double* Bv = d.Bv + cmr * L * Q;
+  const double* Ym = d.Ym + cm * L * NN;
+  const double* Am = d.Am + cm * L * NN;
+  const double* kk = d.kk + cm * L * NP;
+  const double* Ek = d.Ek + cm * L * NP;
+  const double* Bv = d.Bv + cm * L * Q;
   const double* ts0 = d.taus0 + (long)c * (L + 1);
   const double* dq = d.dq + (long)c * L * d.Ns * Q;
-  double* wsb = d.Fws + cmw * Lm1 * Ws<NP>::SLOT;
+  double* wsb = d.Fws + cm * Lm1 * Ws<NP>::SLOT;
   double* coef = d.coef + cm * L * Q;
   const int mg = d.m0 + d.mstep * m;  // the Fourier mode this local index stands for (mode shards)
   const bool iso = d.Ns > 0 && mg == 0;
@@ -1336,731 +1326,15 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
   if (!(fabs(cminus) + fabs(cplus) < 1e300)) rtd_raise(d, RTD_ST_BC, mg, c);
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// Fused boundary-condition kernel for NP = 16 T streams per hemisphere (T x T tiles of 16 x 16, each in the D layout):
-// the 64-stream form (T = 2) of rtd_bc_mfma_kernel -- same recursion, same speculative column elimination, one
-// wavefront per (column, mode); a 32 x 32 matrix is 16 doubles per lane, so the kernel is compiled for one wavefront per
-// SIMD and prefetches the next layer's operands behind the elimination.  An elimination whose speculation fails is redone
-// column-pivoted on an LDS copy of its inputs; a chain that still cannot be solved (singular carry block) raises its flag
-// in `need_split` and leaves, and the row-per-lane kernels (rtd_iface_kernel / rtd_sweep_kernel, partial pivoting) solve
-// the flagged chains afterwards.  T = 1 reproduces the
-// arithmetic of rtd_bc_mfma_kernel (used as a cross-check of this generalisation in the tests, RTD_BC_TILED=1).
-// ------------------------------------------------------------------------------------------------
-// Growth threshold of the tiled kernel's speculative elimination.  A flagged chain is expensive here: it is redone as a
-// whole by the row-per-lane kernels, whose latency per chain (50 layers x 32 pivoted steps) is that of a whole launch.
-// On cfg5 (128 columns = 8 192 chains): threshold 64 flags 507 chains (the pivoted kernels then cost what they cost for all
-// chains, 15 ms), 1e3: 189, 1e5: 4 (2.8 ms), 1e8: none; the error against the reference goldens is 2.19e-10 of the field
-// scale at every one of them (the row-per-lane path alone: 2.1e-9).  1e6 bounds the relative perturbation of a step by
-// ~1e-10; zero pivots and overflow still go to the pivoted kernels through the non-finite check.
-template <int T>
-__global__ __launch_bounds__(64, (T == 1 ? 2 : 1)) void rtd_bc_tile_kernel(RtdDev d, int* need_split) {
-  constexpr int NP = 16 * T, Q = 2 * NP, NN = NP * NP;
-  const int lane = threadIdx.x, kq = lane >> 4, col = lane & 15, rowbase = lane & 48;
-  const long cm = chain_of_block(blockIdx.x, d.C, d.M);
-  const int m = (int)(cm % d.M), c = (int)(cm / d.M);
-  const int L = d.L, Lm1 = L - 1;
-  const double* Ym = d.Ym + cm * L * NN;
-  const double* Am = d.Am + cm * L * NN;
-  const double* kk = d.kk + cm * L * NP;
-  const double* Ek = d.Ek + cm * L * NP;
-  const double* Bv = d.Bv + cm * L * Q;
-  const double* ts0 = d.taus0 + (long)c * (L + 1);
-  const double* dq = d.dq + (long)c * L * d.Ns * Q;
-  double* wsb = d.Fws + cm * Lm1 * Ws<NP>::SLOT;
-  double* coef = d.coef + cm * L * Q;
-  const int mg = d.m0 + d.mstep * m;
-  const bool iso = d.Ns > 0 && mg == 0;
-  const bool beam = d.beam != 0;
-  const double mu0 = beam ? d.mu0[c] : 1.0;
-  const int careful = chain_needs_pivoting(d, iso, kk, L, NP) | (d.flags & 1) | ((d.flags >> 2) & 1);  // (RTD_BC_FORCE_PIVOT: either value)
-  if ((d.flags & 2) && m % 3 == 0) {  // test hook (RTD_BC_FORCE_HANDOVER): every third Fourier mode's chain goes to the pivoted
-    //                                    kernels (by mode, not by chain index: the choice must not depend on the windowing)
-    if (lane == 0) {
-      need_split[cm] = 1;
-      *d.split_any = 1;
-    }
-    return;
-  }
-  // thermal particular solution of layer l at one of the layer's own boundaries (top / bottom), streams idx in [0, 2 NP): the values
-  // the eigen kernel left in vb (it holds the polynomial coefficients about the layer's top, rtd_dd.h) -- no polynomial is evaluated here
-  const double* vbp = d.vb + (long)c * L * 4 * NP;
-  auto vedge = [&](int l, bool bottom, int idx) { return vbp[((long)l * 4 + (bottom ? 2 : 0)) * NP + idx]; };
-  auto load_d = [](const double* p, const int kq, const int col) {  // row-major NP x NP matrix -> tiles in the D layout
-    MatT<T> x;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) x.t[I][J][q] = p[(16 * I + 4 * q + kq) * NP + 16 * J + col];
-    return x;
-  };
-  auto load_row = [](const double* p, const int kq) {
-    RowT<T> x;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) x.r[I][q] = p[16 * I + 4 * q + kq];
-    return x;
-  };
-  auto load_col = [](const double* p, const int col) {
-    ColT<T> x;
-#pragma unroll
-    for (int J = 0; J < T; ++J) x.c[J] = p[16 * J + col];
-    return x;
-  };
-  auto make_eye = [](const int kq, const int col) {
-    MatT<T> e;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) e.t[I][J][q] = (I == J && 4 * q + kq == col) ? 1.0 : 0.0;
-    return e;
-  };
-  auto fail_chain = [&]() {  // this chain could not be solved here: hand it to the row-per-lane kernels
-    if (lane == 0) {
-      need_split[cm] = 1;
-      *d.split_any = 1;  // (they do not evaluate at the interfaces: the evaluation kernel then does it for the window)
-    }
-  };
-  // The inputs of the running elimination, row-major [2 NP + 1][NP] (+1 padding): read back only when its speculation fails.
-  // Then the same elimination is done once more, column-pivoted, straight on this LDS copy: every lane owns a row (rows
-  // lane and lane + 64), a step reads the pivot row, picks the largest unused column, and every lane updates its row.
-  // Slow (~25 us) and rare (1 of 8 192 chains x 50 layers on cfg5 at the growth threshold used).
-  constexpr int LDM = NP + 1, NROW = 2 * NP + 1;
-  __shared__ double sM[NROW * LDM];
-  __shared__ double sF[NP];
-  __shared__ int sPerm[NP];
-  auto save_inputs = [&](const MatT<T>& xa, const MatT<T>& xb, const ColT<T>& xv, const int kq, const int col) {
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          sM[(16 * I + 4 * q + kq) * LDM + 16 * J + col] = xa.t[I][J][q];
-          sM[(NP + 16 * I + 4 * q + kq) * LDM + 16 * J + col] = xb.t[I][J][q];
-        }
-    if (kq == 0)
-#pragma unroll
-      for (int J = 0; J < T; ++J) sM[2 * NP * LDM + 16 * J + col] = xv.c[J];
-  };
-  // -> false when the matrix is singular (no usable pivot); on success xb, xv hold Tb^T Ta^-T and t^T Ta^-T, columns in
-  //    their natural order
-  auto pivoted_redo = [&](MatT<T>& xb, ColT<T>& xv, const int kq, const int col) -> bool {
-    __syncthreads();
-    unsigned long long used = 0;
-    bool ok = true;
-    for (int K = 0; K < NP; ++K) {
-      float key = (lane < NP && !((used >> lane) & 1ull)) ? fabsf((float)sM[K * LDM + lane]) : -1.0f;
-      int idx = lane;
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) {  // wave argmax
-        const float k2 = __shfl_xor(key, o, 64);
-        const int i2 = __shfl_xor(idx, o, 64);
-        if (k2 > key || (k2 == key && i2 < idx)) {
-          key = k2;
-          idx = i2;
-        }
-      }
-      const int pcol = idx;
-      if (!(key > 0.0f)) ok = false;
-      used |= 1ull << pcol;
-      const double piv = sM[K * LDM + pcol];
-      const double rp = 1.0 / piv;
-      if (lane < NP) sF[lane] = (lane == pcol) ? 0.0 : sM[K * LDM + lane] * rp;
-      if (lane == 0) sPerm[K] = pcol;
-      __syncthreads();
-      for (int row = lane; row < NROW; row += 64) {
-        double* r = sM + row * LDM;
-        const double mp = r[pcol];
-        for (int jj = 0; jj < NP; ++jj) r[jj] -= sF[jj] * mp;
-        r[pcol] = mp * rp;
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int J = 0; J < T; ++J) {
-      const int src = sPerm[16 * J + col];  // unknown 16 J + col sits in the column that was the pivot of step 16 J + col
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) xb.t[I][J][q] = sM[(NP + 16 * I + 4 * q + kq) * LDM + src];
-      xv.c[J] = sM[2 * NP * LDM + src];
-    }
-    __syncthreads();
-    return ok;
-  };
-
-  // The chain's small vectors for a window of RTD_BCT_WIN layers in LDS, as in rtd_bc_mfma_kernel: exp(-k dtau), the stream
-  // scaling T, and the particular solution (beam + thermal) as the forward sweep needs it -- its jump r_l at the interface
-  // below layer l (:184-205, :242-245).  The loops then have no global load that is consumed at once.
-  constexpr int W = RTD_BCT_WIN;
-  __shared__ double sPs[W][Q];
-  __shared__ double sEk[W][NP];
-  __shared__ double sT[2][NP];  // T and 1 / T
-  int wb = 0;  // the window holds layers [wb, wb + W)
-  // mode 1: the jump r_l (forward sweep); 2: the particular solution at the top of layer l (the fused evaluation of the
-  // backward sweep); 0: exp(-k dtau) only
-  auto fill = [&](const int base, const int mode) {
-    __syncthreads();
-    wb = base;
-    const int nl = min(W, L - base);
-    // (eight passes of the wavefront at a time, all their loads issued before the first is used -- indices clamped, not
-    //  predicated: a loop of load / wait / write would pay the memory latency once per 64 elements)
-    const double* att = d.att + (long)c * (L + 1);
-    if (mode != 0)
-      for (int e0 = 0; e0 < nl * Q; e0 += 8 * 64) {
-        double b1[8], b0[8], at[8];
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int e = min(e0 + lane + 64 * it, nl * Q - 1), l = base + e / Q, i = e % Q;
-          const int lt = mode == 2 ? l : min(l + 1, Lm1);  // forward: the jump B_(l+1) - B_l (zero at the last layer)
-          b1[it] = Bv[lt * Q + i];
-          b0[it] = Bv[l * Q + i];
-          at[it] = att[mode == 2 ? l : l + 1];
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int e = e0 + lane + 64 * it, l = base + e / Q, i = e % Q;
-          if (e < nl * Q) {
-            double v = beam ? (mode == 2 ? b1[it] : b1[it] - b0[it]) * at[it] : 0.0;
-            if (iso) {
-              if (mode == 2) v += vedge(l, false, i);
-              else if (l < Lm1) v += vedge(l + 1, false, i) - vedge(l, true, i);
-            }
-            (&sPs[0][0])[e] = v;
-          }
-        }
-      }
-    for (int e0 = 0; e0 < nl * NP; e0 += 8 * 64) {
-      double ek[8];
-#pragma unroll
-      for (int it = 0; it < 8; ++it) ek[it] = Ek[(long)base * NP + min(e0 + lane + 64 * it, nl * NP - 1)];
-#pragma unroll
-      for (int it = 0; it < 8; ++it)
-        if (e0 + lane + 64 * it < nl * NP) (&sEk[0][0])[e0 + lane + 64 * it] = ek[it];
-    }
-    __syncthreads();
-  };
-  for (int e = lane; e < NP; e += 64) {
-    const double t = d.T[e];
-    sT[0][e] = t;
-    sT[1][e] = fast_rcp(t);
-  }
-  fill(0, 1);
-
-  MatT<T> a0 = load_d(Am, kq, col), y0 = load_d(Ym, kq, col);
-  const int lsecond = min(1, Lm1);
-  MatT<T> a1 = load_d(Am + (long)lsecond * NN, kq, col), y1 = load_d(Ym + (long)lsecond * NN, kq, col);
-  ColT<T> k0c = load_col(kk, col), k1c = load_col(kk + lsecond * NP, col);
-  ColT<T> rT_col;
-  {
-    const ColT<T> tc = load_col(d.T, col);
-#pragma unroll
-    for (int J = 0; J < T; ++J) rT_col.c[J] = fast_rcp(tc.c[J]);
-  }
-  // carry rows (transposed): top boundary, down-streams at tau = 0 (:161-179, :284-285):
-  //   Ta = Gm_0 = (Y + A/k)/T-rows,  Tb = Gp_0 E_0 = (Y - A/k)/T-rows E_0
-  MatT<T> ta, tb;
-  {
-    const MatT<T> eye = make_eye(kq, col);
-    const MatT<T> yt = mmT<T>(y0, eye), at = mmT<T>(a0, eye);
-    const RowT<T> k_row = load_row(kk, kq), e_row = load_row(&sEk[0][0], kq);
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const double av = at.t[I][J][q] * fast_rcp(k_row.r[I][q]);
-          ta.t[I][J][q] = (yt.t[I][J][q] + av) * rT_col.c[J];
-          tb.t[I][J][q] = (yt.t[I][J][q] - av) * rT_col.c[J] * e_row.r[I][q];
-        }
-  }
-  ColT<T> tv = load_col(d.bneg + cm * NP, col);
-  if (beam) {
-    const ColT<T> b = load_col(Bv + NP, col);
-#pragma unroll
-    for (int J = 0; J < T; ++J) tv.c[J] -= b.c[J];
-  }
-  if (iso) {
-    const ColT<T> b = load_col(dq + NP, col);
-#pragma unroll
-    for (int J = 0; J < T; ++J) tv.c[J] -= b.c[J];
-  }
-
-  // One layer per iteration: loads (layer l + 2's operands, consumed by the NEXT iteration: one wavefront per SIMD, nothing
-  // else hides their latency), the elimination, an explicit wait for the loads and only THEN the stores of H, s, rho_b (with
-  // loads and stores both in flight every wait is a wait for the youngest store's acknowledgement), rho, the carry.
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // nothing of the prologue pending at the loop's entry (see rtd_bc_mfma_kernel)
-  for (int l = 0; l < L; ++l) {
-    int lv = lane;
-    asm volatile("" : "+v"(lv));
-    const int kq = lv >> 4, col = lv & 15, rowbase = lv & 48;
-    const int ln = min(l + 1, Lm1), l2 = min(l + 2, Lm1);
-    const MatT<T> a2 = load_d(Am + (long)l2 * NN, kq, col), y2 = load_d(Ym + (long)l2 * NN, kq, col);
-    const ColT<T> k2c = load_col(kk + l2 * NP, col);
-    if (ln >= wb + W) fill(l, 1);
-    const int r0 = l - wb, r1 = ln - wb;
-    // ---- elimination: [Ta^T ; Tb^T ; t^T] -> H = S^T (in tb), s (in tv)
-    {
-      save_inputs(ta, tb, tv, kq, col);
-      int bad = 0;
-      GjFastT<T, 0>::run(ta, tb, tv, bad, col);
-      auto finite = [&]() {
-        double chk = 0.0;
-#pragma unroll
-        for (int J = 0; J < T; ++J) {
-          chk += fabs(tv.c[J]);
-#pragma unroll
-          for (int I = 0; I < T; ++I) chk += fabs(tb.t[I][J][0]) + fabs(tb.t[I][J][1]) + fabs(tb.t[I][J][2]) + fabs(tb.t[I][J][3]);
-        }
-        return chk < 1e300;
-      };
-      bad |= finite() ? 0 : 1;  // zero pivot: inf / nan
-      bad |= careful;  // (RTD_BC_FORCE_PIVOT, or a chain that hangs on the last digits: chain_needs_pivoting)
-      if (__any(bad)) {  // some diagonal pivot was too small: the pivoted elimination from the saved inputs
-        const bool ok = pivoted_redo(tb, tv, kq, col);
-        if (__any(!ok || !finite())) {
-          fail_chain();
-          return;
-        }
-      }
-    }
-    if (l == Lm1) break;
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the loads of this iteration, before the stores go out
-    double* ws = wsb + (long)l * Ws<NP>::SLOT;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ws[Ws<NP>::S + (16 * I + 4 * q + kq) * NP + 16 * J + col] = tb.t[I][J][q];
-    if (kq == 0)
-#pragma unroll
-      for (int J = 0; J < T; ++J) ws[Ws<NP>::SV + 16 * J + col] = tv.c[J];
-    // ---- rho = G_l^-1 r_l for the particular-solution jump r_l at the interface:
-    //   rho_t/b = 1/4 [ V^-1 (r_up + r_dn) +- U^-1 (r_up - r_dn) ],  V^-1[j][i] = T_i A[i][j],  U^-1[j][i] = -k_j T_i Y[i][j]
-    MatT<T> y0s, a1s;
-#pragma unroll
-    for (int J = 0; J < T; ++J) {
-      const double rk1 = fast_rcp(k1c.c[J]);
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          y0s.t[I][J][q] = y0.t[I][J][q] * k0c.c[J];
-          a1s.t[I][J][q] = a1.t[I][J][q] * rk1;
-        }
-    }
-    ColT<T> rt, rb;
-    {
-      const RowT<T> t_row = load_row(&sT[0][0], kq), ru = load_row(&sPs[r0][0], kq), rd = load_row(&sPs[r0][NP], kq);
-      RowT<T> vs, vd;  // T (r_up + r_dn), -T (r_up - r_dn) in row form
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          vs.r[I][q] = t_row.r[I][q] * (ru.r[I][q] + rd.r[I][q]);
-          vd.r[I][q] = -t_row.r[I][q] * (ru.r[I][q] - rd.r[I][q]);
-        }
-#pragma unroll
-      for (int J = 0; J < T; ++J) {
-        double pa = 0.0, pb = 0.0;
-#pragma unroll
-        for (int I = 0; I < T; ++I)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            pa += a0.t[I][J][q] * vs.r[I][q];
-            pb += y0s.t[I][J][q] * vd.r[I][q];
-          }
-        rt.c[J] = 0.25 * sum_kq(pa + pb);
-        rb.c[J] = 0.25 * sum_kq(pa - pb);
-      }
-      if (kq == 0)
-#pragma unroll
-        for (int J = 0; J < T; ++J) ws[Ws<NP>::RB + 16 * J + col] = rb.c[J];
-    }
-    // ---- carry of the next layer:  Ta'^T = -(Wq^T H E + Wp^T),  Tb'^T = -E' (Wp^T H E + Wq^T)  with
-    //      Wp/Wq = (M1 +- M2s)/2, M1 = A_l^T Y', M2s = diag(k) Y_l^T A' diag(1/k'):  X = M1^T H E, Z = M2s^T H E;
-    //      t' = rho_t - E (s - S rho_b).  Products are formed and consumed one after the other (registers).
-    const ColT<T> e0c = load_col(&sEk[r0][0], col);
-    const RowT<T> e1r = load_row(&sEk[r1][0], kq);
-    ColT<T> tnew;
-    {
-      const ColT<T> srb = col_dotT<T>(tb, col_to_rowT<T>(rb, rowbase, kq));
-#pragma unroll
-      for (int J = 0; J < T; ++J) tnew.c[J] = rt.c[J] - e0c.c[J] * (tv.c[J] - srb.c[J]);
-    }
-    MatT<T> he;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) he.t[I][J][q] = tb.t[I][J][q] * e0c.c[J];
-    // the transposes M1^T, M2s^T through the (now free) save area instead of a second MFMA chain each: FP64 MFMAs occupy the
-    // DP ALUs the vector instructions need (tools/hiptests/dp_coissue.hip); at T = 2 they were 64 of the 192 MFMAs of a layer
-    auto transposedT = [&](const MatT<T>& mm) {
-      MatT<T> t;
-      __syncthreads();
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int J = 0; J < T; ++J)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) sM[(16 * I + 4 * q + kq) * LDM + 16 * J + col] = mm.t[I][J][q];
-      __syncthreads();
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int J = 0; J < T; ++J)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) t.t[I][J][q] = sM[(16 * J + col) * LDM + 16 * I + 4 * q + kq];
-      __syncthreads();
-      return t;
-    };
-    MatT<T> s1;  // X + M1^T
-    {
-      const MatT<T> m1 = mmT<T>(a0, y1);
-      const MatT<T> xx = mmT<T>(m1, he);
-      const MatT<T> m1t = transposedT(m1);
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int J = 0; J < T; ++J)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) s1.t[I][J][q] = xx.t[I][J][q] + m1t.t[I][J][q];
-    }
-    {
-      const MatT<T> m2s = mmT<T>(y0s, a1s);
-      const MatT<T> zz = mmT<T>(m2s, he);
-      const MatT<T> m2st = transposedT(m2s);
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int J = 0; J < T; ++J)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double dd = zz.t[I][J][q] - m2st.t[I][J][q];
-            ta.t[I][J][q] = -0.5 * (s1.t[I][J][q] - dd);
-            tb.t[I][J][q] = -0.5 * (s1.t[I][J][q] + dd) * e1r.r[I][q];
-          }
-    }
-    tv = tnew;
-    a0 = a1;
-    y0 = y1;
-    a1 = a2;
-    y1 = y2;
-    k0c = k1c;
-    k1c = k2c;
-  }
-
-  // ---- bottom boundary (up-streams at tau_L) (:208-232, :248-254, :288-293):  Ba C- + Bb C+ = br,
-  //      with C- = s - S C+  ->  (Bb - Ba S) C+ = br - Ba s;  Ba = [(I - R) P0 - (I + R) Q0] E_L, Bb = (I - R) P0 + (I + R) Q0,
-  //      P0 = Y/T-rows, Q0 = A/(k T-rows), R = (1 + delta_m0) q (mu w).  Solved transposed like the carry.
-  ColT<T> cminus, cplus;
-  {
-    const int l = Lm1;
-    const RowT<T> eLr = load_row(&sEk[l - wb][0], kq), t_row = load_row(&sT[0][0], kq);
-    const ColT<T> kLc = load_col(kk + l * NP, col);
-    const MatT<T> eye = make_eye(kq, col);
-    MatT<T> p0, q0, x1 = eye, x2 = eye, rtr;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const double rTr = fast_rcp(t_row.r[I][q]);
-          p0.t[I][J][q] = y0.t[I][J][q] * rTr;
-          q0.t[I][J][q] = a0.t[I][J][q] * rTr * fast_rcp(kLc.c[J]);
-          rtr.t[I][J][q] = 0.0;
-        }
-    const bool refl = mg < d.NBDRF;
-    if (refl) {
-      const double delta = (mg == 0) ? 2.0 : 1.0;
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int J = 0; J < T; ++J)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int j2 = 16 * I + 4 * q + kq, j = 16 * J + col;  // R^T in the D layout: [row j2][col j] = R[j][j2]
-            const double r = delta * d.bdrfq[(((long)c * d.NBDRF + mg) * NP + j) * NP + j2] * d.mu[j2] * d.w[j2];
-            rtr.t[I][J][q] = r;
-            x1.t[I][J][q] -= r;
-            x2.t[I][J][q] += r;
-          }
-    }
-    const MatT<T> g1 = mmT<T>(p0, x1), g2 = mmT<T>(q0, x2);  // ((I - R) P0)^T, ((I + R) Q0)^T
-    MatT<T> bat, mt;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int J = 0; J < T; ++J)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          bat.t[I][J][q] = eLr.r[I][q] * (g1.t[I][J][q] - g2.t[I][J][q]);
-          mt.t[I][J][q] = g1.t[I][J][q] + g2.t[I][J][q];
-        }
-    {
-      const MatT<T> sd = mmT<T>(tb, eye);   // S in the D layout
-      const MatT<T> hb = mmT<T>(sd, bat);   // S^T Ba^T
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int J = 0; J < T; ++J)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) mt.t[I][J][q] -= hb.t[I][J][q];  // (Bb - Ba S)^T
-    }
-    ColT<T> br = load_col(d.bpos + cm * NP, col);
-    const double tL = ts0[L];
-    const double att = beam ? d.att[(long)c * (L + 1) + L] : 0.0;
-    if (refl) {
-      if (beam) {
-        const ColT<T> rbm = col_dotT<T>(rtr, load_row(Bv + l * Q + NP, kq));
-#pragma unroll
-        for (int J = 0; J < T; ++J) {
-          const double Xs = mu0 * d.I0[c] / M_PI * d.bdrfq0[((long)c * d.NBDRF + mg) * NP + 16 * J + col];
-          br.c[J] += (Xs + rbm.c[J] - Bv[l * Q + 16 * J + col]) * att;
-        }
-      }
-      if (iso) {
-        RowT<T> vr;
-#pragma unroll
-        for (int I = 0; I < T; ++I)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) vr.r[I][q] = vedge(l, true, NP + 16 * I + 4 * q + kq);
-        const ColT<T> rv = col_dotT<T>(rtr, vr);
-#pragma unroll
-        for (int J = 0; J < T; ++J) br.c[J] += rv.c[J] - vedge(l, true, 16 * J + col);
-      }
-    } else {
-#pragma unroll
-      for (int J = 0; J < T; ++J) {
-        if (beam) br.c[J] -= Bv[l * Q + 16 * J + col] * att;
-        if (iso) br.c[J] -= vedge(l, true, 16 * J + col);
-      }
-    }
-    ColT<T> rhs;
-    {
-      const ColT<T> bs = col_dotT<T>(bat, col_to_rowT<T>(tv, rowbase, kq));
-#pragma unroll
-      for (int J = 0; J < T; ++J) rhs.c[J] = br.c[J] - bs.c[J];
-    }
-    {
-      MatT<T> none;
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int J = 0; J < T; ++J) none.t[I][J] = v4f64{0.0, 0.0, 0.0, 0.0};
-      save_inputs(mt, none, rhs, kq, col);
-      int bad = 0;
-      GjFastT<T, 0>::run(mt, none, rhs, bad, col);  // (the updates of the zero block cost 16 T^2 FMAs per step: once per chain)
-      auto finite = [&]() {
-        double chk = 0.0;
-#pragma unroll
-        for (int J = 0; J < T; ++J) chk += fabs(rhs.c[J]);
-        return chk < 1e300;
-      };
-      bad |= finite() ? 0 : 1;
-      bad |= careful;
-      if (__any(bad)) {
-        const bool ok = pivoted_redo(none, rhs, kq, col);
-        if (__any(!ok || !finite())) {
-          fail_chain();
-          return;
-        }
-      }
-    }
-    cplus = rhs;
-    {
-      const ColT<T> sc = col_dotT<T>(tb, col_to_rowT<T>(cplus, rowbase, kq));
-#pragma unroll
-      for (int J = 0; J < T; ++J) cminus.c[J] = tv.c[J] - sc.c[J];
-    }
-  }
-  // ---- backward sweep: C+_l = Wq C-' + Wp E' C+' + rho_b ;  C-_l = s_l - S_l C+_l, with W applied through its factors
-  //      Wq x + Wp y = [A_l^T Y' (x + y) + k_l Y_l^T A' ((y - x)/k')] / 2:  the row sums  w1 = Y' (C-' + E' C+'),
-  //      w2 = A' (E' C+' - C-') / k'  of the layer below are carried from step to step, so that a step touches the operands of
-  //      ONE layer only.  Two operand sets rotate (loop unrolled by two: a renaming, not a copy that would wait for the
-  //      load); the coefficients are staged in the (now free) save area of the elimination and leave as full-width
-  //      stores every NSLOT layers -- a store inside the sweep would turn every wait for an operand into a wait for
-  //      that store's acknowledgement.
-  //      With the fused evaluation (d.um) a slot also takes u^m at the top of the layer: the two row sums ARE those of
-  //      that interface (see rtd_bc_mfma_kernel), plus the particular solution from the window; row L is the bottom of the
-  //      last layer.
-  double* um = d.um ? d.um + cm * (L + 1) * Q : nullptr;
-  constexpr int SLOTW = 2 * Q;  // [C-, C+ | u^m up, down]
-  constexpr int NSLOT = (NROW * LDM) / SLOTW;
-  double* const sOut = sM;
-  int nstage = 0, ltop = L;  // slot s holds the rows of layer / interface ltop - s (row L: u^m only)
-  auto flush = [&]() {
-    __syncthreads();
-#pragma unroll 1
-    for (int s2 = 0; s2 < nstage; ++s2) {
-      const long row = ltop - s2;
-      for (int e = lane; e < SLOTW; e += 64) {
-        const double v = sOut[s2 * SLOTW + e];
-        if (e < Q) {
-          if (row < L) coef[row * Q + e] = v;
-        } else if (um) {
-          um[row * Q + e - Q] = v;
-        }
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __syncthreads();
-    ltop -= nstage;
-    nstage = 0;
-  };
-  // the homogeneous part of u^m from the row sums P = Y_l (e- C- + e+ C+), Qs = A_l (e- C- - e+ C+) / k_l: lanes col < 4 T hold
-  // element i = 16 (col >> 2) + 4 (col & 3) + kq of the up- and of the down-streams
-  auto um_values = [&](const RowT<T>& P, const RowT<T>& Qs, const int kq, const int col, double& up, double& dn) {
-    const RowT<T> rT = load_row(&sT[1][0], kq);
-    up = 0.0;
-    dn = 0.0;
-#pragma unroll
-    for (int I = 0; I < T; ++I)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const bool mine = (col >> 2) == I && (col & 3) == q;
-        const double u_q = (P.r[I][q] - Qs.r[I][q]) * rT.r[I][q], d_q = (P.r[I][q] + Qs.r[I][q]) * rT.r[I][q];
-        up = mine ? u_q : up;
-        dn = mine ? d_q : dn;
-      }
-  };
-  RowT<T> w1, w2;  // w1 = P, w2 = -Qs of the top of the current layer
-  auto stage = [&](const int l, const int kq, const int col) {
-    if (nstage == NSLOT) flush();
-    double* o = sOut + nstage * SLOTW;
-    if (kq == 0)
-#pragma unroll
-      for (int J = 0; J < T; ++J) {
-        o[16 * J + col] = cminus.c[J];
-        o[NP + 16 * J + col] = cplus.c[J];
-      }
-    if (um) {
-      RowT<T> nw2;
-#pragma unroll
-      for (int I = 0; I < T; ++I)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) nw2.r[I][q] = -w2.r[I][q];
-      double up, dn;
-      um_values(w1, nw2, kq, col, up, dn);
-      if (col < 4 * T) {
-        const int i = 16 * (col >> 2) + 4 * (col & 3) + kq;
-        o[Q + i] = up + sPs[l - wb][i];
-        o[Q + NP + i] = dn + sPs[l - wb][NP + i];
-      }
-    }
-    ++nstage;
-  };
-  fill(max(L - W, 0), um ? 2 : 0);
-  auto row_sums = [&](const MatT<T>& yl, const MatT<T>& al, const ColT<T>& kl, const ColT<T>& el) {
-    ColT<T> xpy, ymx;
-#pragma unroll
-    for (int J = 0; J < T; ++J) {
-      const double x = cminus.c[J], y = el.c[J] * cplus.c[J];
-      xpy.c[J] = x + y;
-      ymx.c[J] = (y - x) * fast_rcp(kl.c[J]);
-    }
-    w1 = row_dotT<T>(yl, xpy);
-    w2 = row_dotT<T>(al, ymx);
-  };
-  {
-    const ColT<T> kL = load_col(kk + Lm1 * NP, col), eL = load_col(&sEk[Lm1 - wb][0], col);
-    nstage = 1;  // slot 0 = row L: u^m at tau_L, the bottom of the last layer (e- = E_L, e+ = 1); no coefficients
-    if (um) {
-      ColT<T> spe, dme;
-#pragma unroll
-      for (int J = 0; J < T; ++J) {
-        const double en = eL.c[J] * cminus.c[J], ep = cplus.c[J];
-        spe.c[J] = en + ep;
-        dme.c[J] = (en - ep) * fast_rcp(kL.c[J]);
-      }
-      double up, dn;
-      um_values(row_dotT<T>(y0, spe), row_dotT<T>(a0, dme), kq, col, up, dn);
-      if (col < 4 * T) {
-        const int i = 16 * (col >> 2) + 4 * (col & 3) + kq;
-        if (beam) {
-          const double attv = d.att[(long)c * (L + 1) + L];
-          up += Bv[Lm1 * Q + i] * attv;
-          dn += Bv[Lm1 * Q + NP + i] * attv;
-        }
-        if (iso) {
-          up += vedge(Lm1, true, i);
-          dn += vedge(Lm1, true, NP + i);
-        }
-        sOut[Q + i] = up;
-        sOut[Q + NP + i] = dn;
-      }
-    }
-    row_sums(y0, a0, kL, eL);
-    stage(Lm1, kq, col);
-  }
-  struct BwSet {
-    MatT<T> a, y, h;
-    ColT<T> sl, rb, k;
-  };
-  auto load_set = [&](const int l) {
-    int lv = lane;
-    asm volatile("" : "+v"(lv));
-    const int kq = lv >> 4, col = lv & 15;
-    BwSet s;
-    const double* ws = wsb + (long)l * Ws<NP>::SLOT;
-    s.a = load_d(Am + (long)l * NN, kq, col);
-    s.y = load_d(Ym + (long)l * NN, kq, col);
-    s.h = load_d(ws + Ws<NP>::S, kq, col);
-    s.sl = load_col(ws + Ws<NP>::SV, col);
-    s.rb = load_col(ws + Ws<NP>::RB, col);
-    s.k = load_col(kk + l * NP, col);
-    return s;
-  };
-  auto step = [&](const int l, const BwSet& s) {
-    int lv = lane;
-    asm volatile("" : "+v"(lv));
-    const int kq = lv >> 4, col = lv & 15, rowbase = lv & 48;
-    const ColT<T> t1 = col_dotT<T>(s.a, w1), t2 = col_dotT<T>(s.y, w2);
-    ColT<T> cp;
-#pragma unroll
-    for (int J = 0; J < T; ++J) cp.c[J] = s.rb.c[J] + 0.5 * (t1.c[J] + s.k.c[J] * t2.c[J]);
-    const ColT<T> hc = col_dotT<T>(s.h, col_to_rowT<T>(cp, rowbase, kq));
-#pragma unroll
-    for (int J = 0; J < T; ++J) cminus.c[J] = s.sl.c[J] - hc.c[J];
-    cplus = cp;
-    if (l > 0 || um) row_sums(s.y, s.a, s.k, load_col(&sEk[l - wb][0], col));
-    stage(l, kq, col);
-  };
-  // One pass of the outer loop per window of the small vectors; the requests of the sets are unconditional (past the top
-  // they repeat layer 0) so that the waits stay counted.
-  for (int lhi = Lm1 - 1; lhi >= 0;) {
-    if (lhi < wb) fill(max(lhi - W + 1, 0), um ? 2 : 0);
-    const int llo = wb;
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    BwSet s0 = load_set(lhi);
-    __builtin_amdgcn_sched_barrier(0);
-    BwSet s1 = load_set(max(lhi - 1, 0));
-    __builtin_amdgcn_sched_barrier(0);
-    for (int l = lhi; l >= llo; l -= 2) {
-      step(l, s0);
-      s0 = load_set(max(l - 2, 0));
-      if (l - 1 < llo) break;
-      step(l - 1, s1);
-      s1 = load_set(max(l - 3, 0));
-    }
-    lhi = llo - 1;
-  }
-  flush();
-  double chk = 0.0;
-#pragma unroll
-  for (int J = 0; J < T; ++J) chk += fabs(cminus.c[J]) + fabs(cplus.c[J]);
-  if (!(chk < 1e300)) rtd_raise(d, RTD_ST_BC, mg, c);
+// The row-per-lane pair as a boundary-condition stage of its own (RTD_SMALL_SPLIT, RTD_BC_WIDE_V1): every chain.
+// part 0: interface operators (all interfaces in parallel), 1: carry recursion / bottom BC / backward sweep
+template <int NP>
+void launch_rows(const RtdDev& d, hipStream_t s, int part) {
+  constexpr int GPW = 64 / NP;
+  const long nif = (long)d.C * d.M * (d.L - 1);
+  const int* none = nullptr;
+  if (part == 0 && nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<NP>, dim3((unsigned)((nif + GPW - 1) / GPW)), dim3(64), 0, s, d, none);
+  if (part == 1) hipLaunchKernelGGL(rtd_sweep_kernel<NP>, dim3((unsigned)(((long)d.C * d.M + GPW - 1) / GPW)), dim3(64), 0, s, d, none);
 }
 
 }  // namespace
@@ -2071,83 +1345,45 @@ bool rtd_small_split() {  // RTD_SMALL_SPLIT: 2 ... 16 streams through rtd_iface
 }
 
 bool rtd_bc_fuses_eval(const RtdDev& d) {
-  // the fused kernels -- rtd_bc_small_kernel (NP <= 8), rtd_bc_mfma_kernel and the tiled one at 16 or 32 streams per hemisphere --
-  // write u^m at the interfaces themselves; a window in which the tiled kernel handed a chain to the row-per-lane kernels
+  // the fused kernels -- rtd_bc_small_kernel (NP <= 8), rtd_bc_mfma_kernel (16) and rtd_bc_tile2_kernel (32 streams per hemisphere) --
+  // write u^m at the interfaces themselves; a window in which the 64-stream kernel handed a chain to the row-per-lane kernels
   // (d.split_any) is evaluated by the evaluation kernel instead (rtd_launch_eval)
   return d.NP == 16 || d.NP == 32 || (d.NP <= 8 && !rtd_small_split());
 }
 
 void rtd_launch_bc(const RtdDev& d, hipStream_t s, int part) {
-  // part 0: interface operators (all interfaces in parallel), 1: carry recursion / bottom BC / backward sweep
-  const int gpw = 64 / d.NP;
-  const long nif = (long)d.C * d.M * (d.L - 1);
-  const dim3 gi((unsigned)((nif + gpw - 1) / gpw));
-  const dim3 gs((unsigned)(((long)d.C * d.M + gpw - 1) / gpw));
-  const dim3 gc((unsigned)((long)d.C * d.M));
-  // RTD_BC_TILED=1: the tiled fused kernel also at NP = 16 (T = 1: cross-check of the 64-stream kernel's generalisation)
-  static const bool tiled16 = getenv("RTD_BC_TILED") != nullptr;
-  const int* none = nullptr;
-#define RTD_BC_CASE(NPV)                                                                                    \
-  case NPV:                                                                                                 \
-    if (part == 0 && nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<NPV>, gi, dim3(64), 0, s, d, none);       \
-    if (part == 1) hipLaunchKernelGGL(rtd_sweep_kernel<NPV>, gs, dim3(64), 0, s, d, none);                  \
-    break;
-  // 2 ... 16 streams: one fused kernel (part 1; part 0 is empty) unless RTD_SMALL_SPLIT asks for the separate ones
-#define RTD_BC_SMALL_CASE(NPV)                                                                              \
-  case NPV:                                                                                                 \
-    if (rtd_small_split()) {                                                                                \
-      if (part == 0 && nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<NPV>, gi, dim3(64), 0, s, d, none);     \
-      if (part == 1) hipLaunchKernelGGL(rtd_sweep_kernel<NPV>, gs, dim3(64), 0, s, d, none);                \
-    } else if (part == 1) {                                                                                 \
-      rtd_launch_bc_small(d, s);                                                                            \
-    }                                                                                                       \
-    break;
-  // fused tiled kernel first (part 0); the chains whose speculative elimination failed raise need_split and are solved by
-  // the pivoted row-per-lane kernels (part 1), which leave at once when none of their chains is flagged
-#define RTD_BC_TILED_CASE(NPV, TV)                                                                          \
-  if (part == 0) {                                                                                          \
-    (void)hipMemsetAsync(d.need_split, 0, sizeof(int) * (size_t)d.C * d.M, s);                              \
-    (void)hipMemsetAsync(d.split_any, 0, sizeof(int), s);                                                   \
-    hipLaunchKernelGGL(rtd_bc_tile_kernel<TV>, gc, dim3(64), 0, s, d, d.need_split);                        \
-  } else {                                                                                                  \
-    if (nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<NPV>, gi, dim3(64), 0, s, d, (const int*)d.need_split); \
-    hipLaunchKernelGGL(rtd_sweep_kernel<NPV>, gs, dim3(64), 0, s, d, (const int*)d.need_split);             \
-  }
+  // the fused kernels run in one of the two parts and leave the other empty
+  const long nch = (long)d.C * d.M;
   switch (d.NP) {
-    RTD_BC_SMALL_CASE(4)
-    RTD_BC_SMALL_CASE(8)
-    case 64: {  // 66 ... 128 streams: four wavefronts per chain (rtd_bc_wide.hip) unless RTD_BC_WIDE_V1 asks for the row-per-lane kernels
-      static const bool wide_v1 = getenv("RTD_BC_WIDE_V1") != nullptr;
-      if (!wide_v1) {
-        rtd_launch_bc_wide(d, s, part);
-        break;
-      }
-      if (part == 0 && nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<64>, gi, dim3(64), 0, s, d, none);
-      if (part == 1) hipLaunchKernelGGL(rtd_sweep_kernel<64>, gs, dim3(64), 0, s, d, none);
+    case 4:  // 2 ... 16 streams: one fused kernel unless RTD_SMALL_SPLIT asks for the separate ones
+      if (rtd_small_split()) launch_rows<4>(d, s, part);
+      else if (part == 1) rtd_launch_bc_small(d, s);
       break;
-    }
-    case 16:
-      if (tiled16) {
-        RTD_BC_TILED_CASE(16, 1)
-      } else if (part == 1) {  // the fused MFMA kernel (part 0 is empty)
-        hipLaunchKernelGGL(rtd_bc_mfma_kernel, gc, dim3(64), 0, s, d);
-      }
+    case 8:
+      if (rtd_small_split()) launch_rows<8>(d, s, part);
+      else if (part == 1) rtd_launch_bc_small(d, s);
       break;
-    case 32: {
-      // the lean two-wavefronts-per-SIMD kernel (rtd_bc_tile2.hip) unless RTD_BC_TILE_V1 asks for rtd_bc_tile_kernel<2>
-      static const bool tile_v1 = getenv("RTD_BC_TILE_V1") != nullptr;
-      if (part == 0 && !tile_v1) {
-        (void)hipMemsetAsync(d.need_split, 0, sizeof(int) * (size_t)d.C * d.M, s);
+    case 16:  // 18 ... 32 streams
+      if (part == 1) hipLaunchKernelGGL(rtd_bc_mfma_kernel, dim3((unsigned)nch), dim3(64), 0, s, d);
+      break;
+    case 32:  // 34 ... 64 streams: the fused kernel first (rtd_bc_tile2.hip); the chains it could not solve (singular carry block) raise
+              // need_split and are solved by the pivoted row-per-lane kernels, which leave at once when none of their chains is flagged
+      if (part == 0) {
+        (void)hipMemsetAsync(d.need_split, 0, sizeof(int) * (size_t)nch, s);
         (void)hipMemsetAsync(d.split_any, 0, sizeof(int), s);
         rtd_launch_bc_tile2(d, s);
       } else {
-        RTD_BC_TILED_CASE(32, 2)
+        const long nif = nch * (d.L - 1);
+        if (nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<32>, dim3((unsigned)((nif + 1) / 2)), dim3(64), 0, s, d, (const int*)d.need_split);
+        hipLaunchKernelGGL(rtd_sweep_kernel<32>, dim3((unsigned)((nch + 1) / 2)), dim3(64), 0, s, d, (const int*)d.need_split);
       }
+      break;
+    case 64: {  // 66 ... 128 streams: four wavefronts per chain (rtd_bc_wide.hip) unless RTD_BC_WIDE_V1 asks for the row-per-lane kernels
+      static const bool wide_v1 = getenv("RTD_BC_WIDE_V1") != nullptr;
+      if (wide_v1) launch_rows<64>(d, s, part);
+      else rtd_launch_bc_wide(d, s, part);
       break;
     }
     default: break;
   }
-#undef RTD_BC_CASE
-#undef RTD_BC_SMALL_CASE
-#undef RTD_BC_TILED_CASE
 }

@@ -28,8 +28,8 @@ namespace {
 //     u_up = (p + q)/T + particular, u_down = (p - q)/T + particular -- the interface evaluation costs two extra row sums per
 //     chain (tau = 0 and tau_L); only S_l, s_l, rho_b go through HBM (stored after the loads of an iteration were issued);
 //   * run-path points that are the layer interfaces are written as u^m [c][m][t][2 NP] for rtd_fourier_kernel (d.um).
-// The separate kernels remain: behind RTD_SMALL_SPLIT (A/B, and the suite runs under it), for 66 ... 128 streams and as the
-// tiled kernel's last resort.
+// The separate kernels remain: behind RTD_SMALL_SPLIT (A/B, and the suite runs under it), behind RTD_BC_WIDE_V1 for 66 ... 128
+// streams, and as the 64-stream kernel's last resort.
 // ------------------------------------------------------------------------------------------------
 // Diagnostic build (-DRTD_BCS_STAMPS, never shipped): lane 0 of one wavefront records s_memtime at the phase boundaries of the
 // forward and backward loops and prints the differences (cycles).

@@ -1,26 +1,26 @@
-// rtd_bc_tile2.hip -- the 64-stream boundary-condition kernel in its LEAN form (round 4): two wavefronts per SIMD.
+// rtd_bc_tile2.hip -- the 64-stream boundary-condition kernel: one wavefront per (column, mode), two wavefronts per SIMD.
 //
 // Replaces _solve_for_coeffs (src/PythonicDISORT/_solve_for_coeffs.py:8-390) and the interface values of the closures
-// (_assemble_intensity_and_fluxes.py:221-254) for 32 < NQuad <= 64; same recursion, same speculative elimination and the same
-// matrix-core layout as rtd_bc_tile_kernel<2> (rtd_bc.hip, whose header comment has the mathematics).  What is different:
+// (_assemble_intensity_and_fluxes.py:221-254) for 32 < NQuad <= 64.  The recursion is that of rtd_bc.hip (whose header comment
+// has the mathematics) in the transposed form of rtd_bc_mfma_kernel, on 2 x 2 tiles of 16 x 16 in the matrix-core layout: a
+// 32 x 32 matrix is 16 doubles per lane, a product 64 MFMAs, and the speculative elimination (GjFastT, rtd_bc_tile_common.h)
+// updates both tile columns of a register row by v_fmac_f64_dpp.
 //
-//   rtd_bc_tile_kernel<2> keeps six operand matrices in registers (layers l, l + 1 and the prefetch of l + 2: 192 of its 472
-//   VGPRs), the inputs of the running elimination in a 17 KB LDS save area (read back only when the speculation fails) and the
-//   chain's small vectors in an 18 KB LDS window: ONE wavefront per SIMD, whose dependency stalls nothing hides (VALU issue
-//   30 % + matrix pipe 22 % of the SIMD cycles, profiles/archive/r03_pmc_traffic_cfg5.json), and no room for an eigen-stage wavefront
-//   of the next window beside it.  Here no operand matrix lives across an elimination in more than 64 registers, and a failed
-//   speculation RECOMPUTES its inputs -- from the H, s of the layer above, which the forward sweep stores anyway -- and eliminates
-//   them again with column pivoting IN REGISTERS (GjPivT): no save area.  <= 256 VGPRs and 20 KB of LDS: two chains per SIMD
-//   hide each other's stalls, and the chains that are pivoted throughout (near-conservative mode 0: chain_needs_pivoting) cost
-//   1.3 x instead of 10 x.
+//   No operand matrix lives across an elimination in more than 64 registers, and a failed speculation RECOMPUTES its inputs --
+//   from the H, s of the layer above, which the forward sweep stores anyway -- and eliminates them again with column pivoting IN
+//   REGISTERS (GjPivT): no save area.  That is what keeps the kernel at <= 256 VGPRs and 20 KB of LDS: two chains per SIMD hide
+//   each other's stalls, an eigen-stage wavefront of the next window finds room beside them, and the chains that are pivoted
+//   throughout (near-conservative mode 0: chain_needs_pivoting) cost 1.3 x a speculative chain.  (With one wavefront per SIMD
+//   nothing hides the dependency stalls: VALU issue 30 % + matrix pipe 22 % of the SIMD cycles, measured on this kernel's
+//   predecessor, profiles/archive/r03_pmc_traffic_cfg5.json; that kernel, its 472 VGPRs and its LDS redo are in HISTORY.md.)
+//   A chain that still cannot be solved (singular carry block) raises its flag in need_split and leaves; the row-per-lane
+//   kernels of rtd_bc.hip (partial pivoting) solve the flagged chains afterwards.
 //   End of round 5 (profiles/r05_bc_tile2_phases.txt): what the carry across an interface reads -- Y, A of the layer below and the
 //   interface's vectors -- arrives by LDS-DMA (global_load_lds_dwordx4: no registers, no wait) while the elimination above runs;
 //   the carry's only wait finds requests that are an elimination old, H and s are stored BEHIND it (loads, stores and the DMA share
 //   one in-order counter: the ~80 vector loads that used to follow the stores each waited for a store's acknowledgement), and the
 //   next carry takes its own layer's Y, A from the same LDS images: every matrix is fetched once per forward sweep.  The backward
 //   sweep requests a step ahead in the same way.
-//
-// rtd_bc_tile_kernel<2> stays selectable (RTD_BC_TILE_V1=1: A/B runs, and the suite passes under it).
 #include <cstdlib>
 #include <type_traits>
 
@@ -53,7 +53,7 @@ using Col = ColT<2>;
 
 // Column-pivoted Gauss-Jordan on the stacked rows [Ta^T ; Tb^T (WITH_TB) ; t^T] in registers, 2 x 2 tiles in the D layout:
 // step K makes row K of Ta^T a unit vector; the pivot is the largest unused column of that row with threshold 1/4 in favour
-// of the diagonal (the rule of the LDS redo of rtd_bc_tile_kernel and of GjPiv at 32 streams).  One chain per wavefront:
+// of the diagonal (the rule of GjPiv at 32 streams, rtd_bc.hip, whose comment has the reason).  One chain per wavefront:
 // the pivot column is wave-uniform -- its row entry by v_readlane, its column by ds_bpermute; the pivot column is scaled by
 // 1 / pivot exactly.  Afterwards the column that was the pivot of step c holds unknown c (sPerm[c]): unpermute() moves them back.
 template <bool WITH_TB, int K>

@@ -1,5 +1,5 @@
-// rtd_bc_tile_common.h -- helpers of the matrix-core-layout boundary-condition kernels (rtd_bc.hip: rtd_bc_mfma_kernel,
-// rtd_bc_tile_kernel<T>; rtd_bc_tile2.hip: the lean 64-stream kernel): 16 x 16 tiles in the operand / accumulator layout of
+// rtd_bc_tile_common.h -- helpers of the matrix-core-layout boundary-condition kernels (rtd_bc.hip: rtd_bc_mfma_kernel, 32 streams;
+// rtd_bc_tile2.hip: rtd_bc_tile2_kernel, 64 streams): 16 x 16 tiles in the operand / accumulator layout of
 // v_mfma_f64_16x16x4_f64 ("D layout": lane = 16 kq + col, register q holds element [4 q + kq][col]), products, row / column
 // sums, the speculative tiled elimination and the rule for chains that are pivoted throughout.  Included inside each file's
 // anonymous namespace, after rtd_bc_common.h.
@@ -79,7 +79,7 @@ __device__ __forceinline__ double readlane_f64(const double v, const int lane_un
                                        not.  Round 3 measured what it buys -- the near-conservative beam cases go from <= 1.5e-9 to
                                        <= 5e-12 of their 40-digit solutions -- and what it cost with the LDS redo: 219 k -> 71 k col/s on a
                                        batch with a conservative cloud layer in every column; with GjPiv (registers) it is the default.
-                                       The tiled 64-stream kernel keeps the thermal-only rule (its pivoted path is the LDS redo). */
+                                       The 64-stream kernel (rtd_bc_tile2_kernel) follows the same switch: it pivots in registers too (GjPivT). */
 #endif
 // Which chain (column c, local mode m: index c M + m) a workgroup takes.  Mode 0 of every column first, then the other modes column
 // by column: the chains that are pivoted throughout (above: mode 0 only) take 3 ... 7 times as long as the others, and handed out in
@@ -105,11 +105,15 @@ __device__ __forceinline__ int chain_needs_pivoting(const RtdDev& d, const bool 
   return careful;
 }
 
+// Growth threshold of the tiled (64-stream) kernel's speculative elimination; rtd_bc_mfma_kernel's is RTD_GJ_GROWTH = 64.  Measured
+// on an early form of the tiled kernel, where a flagged chain was expensive: it was redone as a whole by the row-per-lane
+// kernels, whose latency per chain (50 layers x 32 pivoted steps) is that of a whole launch.
+// On cfg5 (128 columns = 8 192 chains): threshold 64 flags 507 chains (the pivoted kernels then cost what they cost for all
+// chains, 15 ms), 1e3: 189, 1e5: 4 (2.8 ms), 1e8: none; the error against the reference goldens is 2.19e-10 of the field
+// scale at every one of them (the row-per-lane path alone: 2.1e-9).  1e6 bounds the relative perturbation of a step by
+// ~1e-10; zero pivots and overflow still reach a pivoted elimination through the non-finite check.
 #ifndef RTD_GJ_GROWTH_TILED
 #define RTD_GJ_GROWTH_TILED 1e6
-#endif
-#ifndef RTD_BCT_WIN
-#define RTD_BCT_WIN 24  // layers of small vectors resident in LDS (T = 2: 18 KB next to the 17 KB save area, 4 wavefronts per CU)
 #endif
 template <int T> struct MatT { v4f64 t[T][T]; };  // t[I][J][q] at lane (kq, col) = element [16 I + 4 q + kq][16 J + col]
 template <int T> struct RowT { v4f64 r[T]; };     // vector in row form:    r[I][q] = v[16 I + 4 q + kq], same in every column

@@ -1742,14 +1742,10 @@ void rtd_launch_eig(const RtdDev& d, hipStream_t s, int part) {
   case NPV:                                                                                      \
     hipLaunchKernelGGL((rtd_eigen_kernel<NPV, 2>), grid, dim3(64), RTD_EIG_LDS_PAD, s, d);       \
     break;
-  // 2 ... 8 streams: the one-lane-per-problem kernel (rtd_eig_small.hip) unless RTD_EIG_SMALL_V1 asks for rtd_eigen_kernel<4, 2>
-  static const bool small_v1 = getenv("RTD_EIG_SMALL_V1") != nullptr;
-  if (d.NP == 4 && !small_v1) {
-    rtd_launch_eig_small(d, s);
-    return;
-  }
   switch (d.NP) {
-    RTD_EIG_CASE(4)
+    case 4:  // 2 ... 8 streams: the one-lane-per-problem kernel (rtd_eig_small.hip)
+      rtd_launch_eig_small(d, s);
+      break;
     RTD_EIG_CASE(8)
     case 16:
       if (mfma) hipLaunchKernelGGL((rtd_eigen_kernel<16, 3>), grid, dim3(64), 0, s, d);

@@ -21,9 +21,7 @@
 // with nothing to hide the latency of its dependent FP64 chains, and 2 048 wavefronts are two rounds of that: the per-problem
 // instruction count fell (13 600 per 64 problems against 3 100 per 8) but the kernel left the issue-bound regime.  The NP = 8
 // instance is therefore not built into the library (RTD_EIG_LANE8 in the launcher's place would be one line); 10 ... 16 streams
-// stay on rtd_eigen_kernel<8, 2>.
-//
-// rtd_eigen_kernel<4, 2> stays selectable (RTD_EIG_SMALL_V1=1: A/B runs, and the suite passes under it).
+// stay on rtd_eigen_kernel<8, 2>.  (The NP = 4 instance of rtd_eigen_kernel is no longer built: HISTORY.md.)
 #include <cstdlib>
 #include <type_traits>
 

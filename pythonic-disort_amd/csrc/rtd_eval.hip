@@ -370,10 +370,9 @@ void rtd_launch_eval(const RtdDev& d, const RtdEval& e, hipStream_t s) {
     else if (d.NP == 8) hipLaunchKernelGGL(rtd_fourier_kernel<8>, g, dim3(EVAL_THREADS), 0, s, d, e);
     else if (d.NP == 16) hipLaunchKernelGGL(rtd_fourier_kernel<16>, g, dim3(EVAL_THREADS), 0, s, d, e);
     else hipLaunchKernelGGL(rtd_fourier_kernel<32>, g, dim3(EVAL_THREADS), 0, s, d, e);
-    // the tiled kernel may have handed chains to the row-per-lane kernels (singular carry blocks; a test hook): those leave
+    // the 64-stream kernel may have handed chains to the row-per-lane kernels (singular carry blocks; a test hook): those leave
     // no u^m, the flag is set, the Fourier-sum kernel has left at once and the evaluation kernel does the window
-    static const bool tiled16 = getenv("RTD_BC_TILED") != nullptr;
-    if (d.NP != 32 && !tiled16) return;
+    if (d.NP != 32) return;
     RtdEval g2 = e;
     g2.um_in = nullptr;
     g2.run_if_set = d.split_any;

@@ -1007,20 +1007,18 @@ def test_fused_bc_kernel_pivoted_path_on_goldens(how):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("switch", ["RTD_EIG_MFMA", "RTD_BC_TILED", "RTD_BC_FORCE_HANDOVER", "RTD_NO_PIPELINE", "RTD_SMALL_SPLIT", "RTD_BC_TILE_V1", "RTD_EIG_SMALL_V1", "RTD_BC_WIDE_V1"])
+@pytest.mark.parametrize("switch", ["RTD_EIG_MFMA", "RTD_BC_FORCE_HANDOVER", "RTD_NO_PIPELINE", "RTD_SMALL_SPLIT", "RTD_BC_WIDE_V1"])
 def test_alternative_kernel_paths_stay_correct(switch):
     """The runtime switches that select an alternative path -- RTD_EIG_MFMA=1: the assembly of Pm, Qm as rank-4 MFMA updates
-    (32 streams); RTD_BC_TILED=1: the tiled fused kernel (the 64-stream kernel) with one tile, in place of the 32-stream
-    kernel it generalises; RTD_BC_FORCE_HANDOVER=1: the tiled kernel hands every third Fourier mode's chain to the pivoted
+    (32 streams); RTD_BC_FORCE_HANDOVER=1: the tiled (64-stream) kernel hands every third Fourier mode's chain to the pivoted
     row-per-lane kernels (its last resort for singular carry blocks; the window's fused interface evaluation is then
     replaced by the evaluation kernel); RTD_NO_PIPELINE=1: the windows of a plan one after the other on one stream instead
     of the two-stream pipeline; RTD_SMALL_SPLIT=1: 2 ... 16 streams through the separate interface / sweep / evaluation kernels
-    of rounds 1-3 instead of the fused rtd_bc_small_kernel (round 4); RTD_BC_TILE_V1=1: 64 streams through rtd_bc_tile_kernel<2>
-    (one wavefront per SIMD) instead of the lean rtd_bc_tile2_kernel; RTD_EIG_SMALL_V1=1: 2 ... 8 streams through
-    rtd_eigen_kernel<4, 2> instead of the one-lane-per-problem eigen kernel; RTD_BC_WIDE_V1=1: 66 ... 128 streams through the
+    of rounds 1-3 instead of the fused rtd_bc_small_kernel (round 4); RTD_BC_WIDE_V1=1: 66 ... 128 streams through the
     row-per-lane kernels (one wavefront per chain) instead of the four-wavefronts-per-chain kernels of rtd_bc_wide.hip -- pass the golden replay (it has 40-, 48- and 64-stream cases), the synthetic configs incl.
     cfg5, the random cases, the windowed plans and the fused-evaluation comparison.  (Round 3 removed the switches whose
-    paths had lost every A/B: RTD_BC_SPLIT at 32 streams, RTD_EIG_V1, RTD_BCF_WAVES3.)"""
+    paths had lost every A/B: RTD_BC_SPLIT at 32 streams, RTD_EIG_V1, RTD_BCF_WAVES3; the kernels that round 4 superseded went
+    the same way later, with their three switches: HISTORY.md.)"""
     import subprocess
     import sys
     env = dict(os.environ, **{switch: "1"})
@@ -1028,14 +1026,13 @@ def test_alternative_kernel_paths_stay_correct(switch):
                         os.path.join(os.path.dirname(__file__), "test_gpu_parity.py"),
                         os.path.join(os.path.dirname(__file__), "test_gpu_random_parity.py"),
                         "-k", "reference_golden or synthetic_config or random_many or edge_cases or fused_interface or windowed or layer_shards"
-                              + (" or stamnes or cfg3 or random or mode_shards or failed_column or failure_in" if switch in ("RTD_SMALL_SPLIT", "RTD_EIG_SMALL_V1") else "")
-                              + (" or random_64 or cfg5 or high_precision_truth_56" if switch == "RTD_BC_TILE_V1" else "")
+                              + (" or stamnes or cfg3 or random or mode_shards or failed_column or failure_in" if switch == "RTD_SMALL_SPLIT" else "")
                               + (" or beyond_64 or random_128 or random_many" if switch == "RTD_BC_WIDE_V1" else "")],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    if switch in ("RTD_EIG_MFMA", "RTD_NO_PIPELINE", "RTD_BC_TILE_V1", "RTD_BC_WIDE_V1"):
+    if switch in ("RTD_EIG_MFMA", "RTD_NO_PIPELINE", "RTD_BC_WIDE_V1"):
         # round 6: the retained forms under the switches that change the eigen stage (RTD_EIG_MFMA has its own reading of the lean
-        # form's chunk lists), the window pipeline, or the consumers of the hand-off at 64 / 96 streams
+        # form's chunk lists), the window pipeline, or the consumers of the hand-off at 96 streams
         r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
                             os.path.join(os.path.dirname(__file__), "test_gpu_retained.py"), "-k", "windowed_plan or lean_plan or auto_retention"],
                            env=env, capture_output=True, text=True, timeout=1200)
@@ -1265,6 +1262,36 @@ def test_cfg5_windowed_plan_with_forced_handover():
                         os.path.abspath(__file__), "-k", "test_cfg5_windowed_plan_equals_single_window"],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_64_stream_dispatch_and_handover_count(amd, monkeypatch):
+    """The host side of the 64-stream path at its smallest: 2 columns x 3 layers x 40 streams (padded to NP = 32) x 4 Fourier
+    modes, Henyey-Greenstein.  An ordinary solve hands no chain over (rtd_plan_pivoted_chains: 0).  A plan created with
+    RTD_BC_FORCE_HANDOVER=1 in the environment hands over the local modes 0 and 3 of both columns -- 4 chains -- to
+    rtd_iface_kernel<32> / rtd_sweep_kernel<32>, and its interface points come from the evaluation kernel.  Both agree with the
+    oracle at the bound of the synthetic configs; the two eliminations differ, so they are not compared bit for bit."""
+    from pydisort_amd import synthetic
+    from oracle import disort_oracle as O
+    C, M = 2, 4
+    cfg = synthetic.cfg4_columns(C, L=3, NQuad=40)
+    tau = np.concatenate((np.zeros((C, 1)), cfg["tau_arr"]), axis=1)  # tau = 0, both interfaces, the bottom
+    phi = np.array([0.0, 1.0, np.pi])
+    want = [O.pydisort(**synthetic.column_kwargs(cfg, i), NFourier=M)[4](tau[i], phi) for i in range(C)]
+    for forced, chains in ((False, 0), (True, 4)):
+        if forced:
+            monkeypatch.setenv("RTD_BC_FORCE_HANDOVER", "1")
+        _, sol = amd.pydisort_batch(NFourier=M, **cfg)
+        sol.plan.set_eval_points(tau, phi)  # the interfaces: the fused evaluation, or the evaluation kernel once a chain was handed over
+        sol.plan.run()
+        u = sol.plan.fetch()["u"]
+        assert sol.plan.pivoted_chains() == chains, (forced, sol.plan.pivoted_chains())
+        for i in range(C):
+            err, err_pw = goldens.max_rel_err(u[i], want[i])
+            print(f"forced handover {forced}, column {i}: {err:.2e} of the scale, {err_pw:.2e} pointwise")
+            assert err < TOL, (forced, i, err)
+            assert err_pw < PW_TOL, (forced, i, err_pw)
+        sol.plan.close()
 
 
 @pytest.mark.gpu
