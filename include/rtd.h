@@ -293,9 +293,9 @@ int rtd_solve_tensors(const rtd_dims* dims, int32_t device, const rtd_inputs* in
 int rtd_plan_enable_timing(rtd_plan* plan, int32_t enable);
 /* accumulated milliseconds per kernel slot since the last reset (slot names as returned by the Python wrapper):
  * [0] "tables" Legendre tables; [2] "jacobi" the fused rtd_eigen_kernel; [1] "asm" and [3] "post" are the empty slots of
- * the earlier three-kernel eigen stage; [4] "iface" rtd_iface_kernel -- or, at 64 streams, the tiled fused
- * rtd_bc_tile2_kernel; [5] "sweep" rtd_sweep_kernel -- or the fused rtd_bc_mfma_kernel when 16 < NQuad <= 32 (slot 4 is
- * then empty) -- or, at 64 streams, the pivoted kernels' pass over the chains the tiled kernel flagged; [6] "eval"
+ * the earlier three-kernel eigen stage; [4] "iface" the interface kernel of 66 ... 128 streams -- or, at 64 streams, the tiled fused
+ * rtd_bc_tile2_kernel; [5] "sweep" the sweep kernel of 66 ... 128 streams -- or the fused rtd_bc_small_kernel / rtd_bc_mfma_kernel
+ * when NQuad <= 32 (slot 4 is then empty) -- or, at 64 streams, the pivoted kernels' pass over the chains the tiled kernel flagged; [6] "eval"
  * rtd_eval_kernel or, with the fused interface evaluation, rtd_fourier_kernel, plus the NT corrections.  Launches counted in nlaunch[7] (one per window of columns).  Synchronises; with timing
  * enabled every window starts with a stream synchronisation: a measurement mode, not the throughput path. */
 int rtd_plan_get_timing(rtd_plan* plan, double ms[7], int64_t nlaunch[7], int32_t reset);
@@ -383,11 +383,7 @@ enum {
  *                         path of a failed speculation); =2 every chain of the 32-stream kernel takes the register-resident
  *                         column-pivoted elimination throughout (the path of near-conservative mode-0 chains)
  *   RTD_BC_FORCE_HANDOVER tiled (64-stream) kernel: every third chain goes to the pivoted row-per-lane kernels
- *   RTD_BC_WIDE_V1        66 ... 128 streams through the row-per-lane kernels (one wavefront per chain, rounds 1-3) instead of the
- *                         four-wavefronts-per-chain kernels of rtd_bc_wide.hip (round 4)
  *   RTD_EIG_MFMA          eigen stage with its assembly GEMMs on the matrix cores (measured slower; a tested variant)
- *   RTD_SMALL_SPLIT       2 ... 16 streams through the separate interface / sweep / evaluation kernels instead of the fused
- *                         rtd_bc_small_kernel
  *   RTD_RCCL_STUB         TESTS ONLY: path of a stand-in for the RCCL entry points (tests/stub/librccl_stub.so) for rank processes
  *                         that share one GPU, where RCCL itself refuses a second rank; rtd_comm_transport() then says "stub"
  *   RTD_DEBUG             diagnostics on stderr

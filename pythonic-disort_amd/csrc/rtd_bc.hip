@@ -18,15 +18,11 @@
 //   banded matrix to <= 5e-13 on every golden case and on thick/thin/near-conservative stress cases
 //   (tools/proto_device_algo.py: check_structured).
 //
-// Two implementations live in this file.  16 < NQuad <= 32: rtd_bc_mfma_kernel, one wavefront per (column, mode), everything in
-// the matrix-core register layout (see its comment below).  The row-per-lane pair: rtd_iface_kernel (all (column, mode,
-// interface) in parallel: Wp, Wq, rho through HBM) and rtd_sweep_kernel (per (column, mode): forward carry recursion,
-// bottom boundary, backward sweep); NP lanes per problem, 64/NP problems per wavefront, lane i owns row i of the carry
-// system, partial pivoting.  It is the last resort of the 64-stream kernel for a singular carry block (NP = 32, flagged chains
-// only) and, at NP = 4, 8 and 64, what RTD_SMALL_SPLIT / RTD_BC_WIDE_V1 select instead of the fused kernels.
-// The other stream counts have files of their own, all on this recursion: NQuad <= 16 rtd_bc_small.hip, 32 < NQuad <= 64
-// rtd_bc_tile2.hip (rtd_bc_mfma_kernel's scheme on 2 x 2 tiles), 64 < NQuad <= 128 rtd_bc_wide.hip; rtd_launch_bc at the end
-// of this file chooses.  (Kernels that lost their A/B runs and were removed: HISTORY.md.)
+// This file: 16 < NQuad <= 32, rtd_bc_mfma_kernel -- one wavefront per (column, mode), everything in the matrix-core register
+// layout (see its comment below) -- and rtd_launch_bc at the end, which chooses among the files.  The other stream counts have
+// files of their own, all on this recursion: NQuad <= 16 rtd_bc_small.hip, 32 < NQuad <= 64 rtd_bc_tile2.hip (rtd_bc_mfma_kernel's
+// scheme on 2 x 2 tiles) with rtd_bc_rows.hip (row-per-lane kernels with partial pivoting: its last resort for a singular carry
+// block), 64 < NQuad <= 128 rtd_bc_wide.hip.  (Kernels that lost their A/B runs and were removed: HISTORY.md.)
 #include <cstdlib>
 #include <type_traits>
 
@@ -35,486 +31,7 @@
 namespace {
 
 #include "rtd_bc_common.h"
-
-// ------------------------------------------------------------------------------------------------
-// Interface kernel: per (c, m, l < L-1):  Wp, Wq, rho_t, rho_b.
-// ------------------------------------------------------------------------------------------------
-template <int NP>
-__global__ __launch_bounds__(64) void rtd_iface_kernel(RtdDev d, const int* only) {  // only != null: flagged (c, m) chains
-  constexpr int GPW = 64 / NP, LD = NP + 1, Q = 2 * NP;
-  __shared__ double sA[GPW][NP * LD];  // A_l  (natural [i][j])
-  __shared__ double sY[GPW][NP * LD];  // Y_l
-  const int grp = threadIdx.x / NP, j = threadIdx.x % NP;
-  const int Lm1 = d.L - 1;
-  const long nprob = (long)d.C * d.M * Lm1;
-  long pid = (long)blockIdx.x * GPW + grp;
-  bool valid = pid < nprob;
-  if (!valid) pid = nprob - 1;
-  if (only != nullptr) {  // only the chains handed over by the tiled kernel: the others keep what that kernel stored
-    valid = valid && only[pid / Lm1] != 0;
-    const unsigned long long want = __ballot(valid);
-    if (want == 0) return;
-    // groups with nothing to do redo the work of one that has (well-defined data, no stores)
-    const int src = __ffsll((long long)want) - 1;
-    const int pid_w = __shfl((int)pid, src, 64);
-    if (!valid) pid = pid_w;
-  }
-  const int l = (int)(pid % Lm1);
-  const long cm = pid / Lm1;
-  const int m = (int)(cm % d.M), c = (int)(cm / d.M);
-  const long p0 = cm * d.L + l, p1 = p0 + 1;
-  double* A0 = sA[grp];
-  double* Y0 = sY[grp];
-  {
-    const double* Am = d.Am + p0 * NP * NP;
-    const double* Ym = d.Ym + p0 * NP * NP;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      A0[i * LD + j] = Am[i * NP + j];
-      Y0[i * LD + j] = Ym[i * NP + j];
-    }
-  }
-  // V^-1 V' = A^T Y'   and   U^-1 U' = diag(k) Y^T A' diag(1/k')   (T cancels)
-  const double rk1 = 1.0 / d.kk[p1 * NP + j];
-  double* ws = d.Fws + (cm * Lm1 + l) * Ws<NP>::SLOT;
-  if constexpr (NP <= 32) {
-    // column j of Y' and A' of layer l+1
-    double ycol[NP], acol[NP];
-    {
-      const double* Ym = d.Ym + p1 * NP * NP;
-      const double* Am = d.Am + p1 * NP * NP;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        ycol[i] = Ym[i * NP + j];
-        acol[i] = Am[i * NP + j];
-      }
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int r = 0; r < NP; ++r) {
-      double vv = 0.0, uu = 0.0;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        vv += A0[i * LD + r] * ycol[i];
-        uu += Y0[i * LD + r] * acol[i];
-      }
-      uu *= d.kk[p0 * NP + r] * rk1;
-      if (valid) {
-        ws[Ws<NP>::WP + r * NP + j] = 0.5 * (vv + uu);
-        ws[Ws<NP>::WQ + r * NP + j] = 0.5 * (vv - uu);
-      }
-    }
-  } else {
-    // 128 streams: one product at a time (a column of 64 doubles each: both at once do not fit the register file); the
-    // first product waits in the Wp slot
-    __syncthreads();
-    double col[NP];
-    {
-      const double* Ym = d.Ym + p1 * NP * NP;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) col[i] = Ym[i * NP + j];
-    }
-#pragma unroll 2
-    for (int r = 0; r < NP; ++r) {
-      double vv = 0.0;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) vv += A0[i * LD + r] * col[i];
-      if (valid) ws[Ws<NP>::WP + r * NP + j] = vv;
-    }
-    {
-      const double* Am = d.Am + p1 * NP * NP;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) col[i] = Am[i * NP + j];
-    }
-#pragma unroll 2
-    for (int r = 0; r < NP; ++r) {
-      double uu = 0.0;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) uu += Y0[i * LD + r] * col[i];
-      uu *= d.kk[p0 * NP + r] * rk1;
-      if (valid) {
-        const double vv = ws[Ws<NP>::WP + r * NP + j];  // (this lane's own store)
-        ws[Ws<NP>::WP + r * NP + j] = 0.5 * (vv + uu);
-        ws[Ws<NP>::WQ + r * NP + j] = 0.5 * (vv - uu);
-      }
-    }
-  }
-  // particular-solution jump r_l at the interface (:184-205, :242-245) and rho = G_l^-1 r_l:
-  //   rho_t/b = 1/4 [ V^-1 (r_up + r_dn) +- U^-1 (r_up - r_dn) ],  V^-1[j][i] = T_i A[i][j],  U^-1[j][i] = -k_j T_i Y[i][j]
-  const double* ts0 = d.taus0 + (long)c * (d.L + 1);
-  const double tb = ts0[l + 1];
-  const double att = d.beam ? exp(-tb / d.mu0[c]) : 0.0;
-  const int mg = d.m0 + d.mstep * m;  // the Fourier mode this local index stands for (mode shards)
-  const bool iso = d.Ns > 0 && mg == 0;
-  const double kj = d.kk[p0 * NP + j];
-  double rt = 0.0, rb = 0.0;
-#pragma unroll 4
-  for (int i = 0; i < NP; ++i) {
-    double ru = 0.0, rd = 0.0;
-    if (d.beam) {
-      ru = (d.Bv[p1 * Q + i] - d.Bv[p0 * Q + i]) * att;
-      rd = (d.Bv[p1 * Q + NP + i] - d.Bv[p0 * Q + NP + i]) * att;
-    }
-    if (iso) {  // v_{l+1} at its top minus v_l at its bottom: the eigen kernel's boundary values (vb), no polynomial evaluated here
-      const double* vb0 = d.vb + ((long)c * d.L + l) * 4 * NP;
-      ru += vb0[4 * NP + i] - vb0[2 * NP + i];
-      rd += vb0[5 * NP + i] - vb0[3 * NP + i];
-    }
-    const double Ti = d.T[i];
-    const double a = Ti * A0[i * LD + j] * (ru + rd), b = -kj * Ti * Y0[i * LD + j] * (ru - rd);
-    rt += a + b;
-    rb += a - b;
-  }
-  if (valid) {
-    ws[Ws<NP>::RT + j] = 0.25 * rt;
-    ws[Ws<NP>::RB + j] = 0.25 * rb;
-  }
-}
-
-// 128 streams (NP = 64, one chain per wavefront): the rows [Ta | Tb | t] live in LDS, not in registers (64 fully unrolled
-// pivot steps over 129 registers per lane spilled 267 registers and 256 KB of code per elimination), and the elimination is a
-// rolled loop: step K reads the pivot row as LDS broadcasts and updates the own row in place; the pivot row is scaled by the
-// same FMA (f = 1 - 1/pivot on the pivot lane).  Columns (K, NP) and [x0, x1) of the rows are updated.
-template <bool IN_LDS, typename A>
-__device__ __forceinline__ decltype(auto) pick_row(A& regs, double* lds) {
-  if constexpr (IN_LDS) return lds;
-  else return (regs);
-}
-__device__ __forceinline__ void gj_rows_in_lds(double* R, const int ldr, const int j, const int x0, const int x1, int& pc) {
-  constexpr int NP = 64;
-  double* row = R + j * ldr;
-  for (int K = 0; K < NP; ++K) {
-    const float key = (pc < 0) ? fabsf((float)row[K]) : -1.0f;
-    const float kmax = group_max_key<NP>(key);
-    const unsigned long long bal = __ballot(key == kmax);
-    const int found = __ffsll((long long)bal) - 1;  // pivot lane (wave-uniform); -1: a chain that has gone NaN
-    const bool isp = j == found;
-    const int src = found < 0 ? 0 : found;
-    const double* prow = R + src * ldr;
-    const double rp = fast_rcp(prow[K]);
-    const double f = isp ? 1.0 - rp : row[K] * rp;
-    if (isp) pc = K;
-    // eight columns at a time, every load of a batch issued before its first store: the rows may alias each other for the
-    // compiler, element by element every update waited for two LDS round trips (columns below K + 1 that a batch touches are
-    // dead: nothing reads them again)
-    auto batch = [&](const int c0) {
-      double pv[8], rv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pv[e] = prow[c0 + e];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) rv[e] = row[c0 + e];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) row[c0 + e] = fma(-f, pv[e], rv[e]);
-    };
-    for (int c0 = (K + 1) & ~7; c0 < NP; c0 += 8) batch(c0);
-    int c = x0;
-    for (; c + 8 <= x1; c += 8) batch(c);
-    for (; c < x1; ++c) row[c] -= f * prow[c];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Sweep kernel: per (c, m): forward carry recursion over the layers, bottom BC, backward sweep.
-// ------------------------------------------------------------------------------------------------
-template <int NP>
-__global__ __launch_bounds__(64, (NP <= 8 ? RTD_SWEEP_WAVES : (NP == 16 ? 2 : 1))) void rtd_sweep_kernel(RtdDev d, const int* only) {
-  constexpr int GPW = 64 / NP, LD = NP + 1, Q = 2 * NP;
-  constexpr bool ROWS_IN_LDS = NP == 64;  // (see gj_rows_in_lds; the whole wavefront is one chain there: Wq, Wp are wave-uniform
-                                          //  and come as scalar loads, not through LDS: two workgroups fit a CU)
-  __shared__ double sA[GPW][ROWS_IN_LDS ? 1 : NP * LD];  // Wq (forward) / S (bottom)
-  __shared__ double sB[GPW][ROWS_IN_LDS ? 1 : NP * LD];  // Wp
-  __shared__ double sV[GPW][4][NP];
-  constexpr int LDR = 2 * NP + 3;         // [Ta | Tb | t | bottom right-hand side], odd
-  __shared__ double sR[ROWS_IN_LDS ? NP * LDR : 1];
-  const int grp = threadIdx.x / NP, j = threadIdx.x % NP;
-  const long nprob = (long)d.C * d.M;
-  long cm = (long)blockIdx.x * GPW + grp;
-  bool valid = cm < nprob;
-  if (!valid) cm = nprob - 1;
-  if (only != nullptr) {  // only the chains handed over by the tiled kernel: the others keep what that kernel stored
-    valid = valid && only[cm] != 0;
-    const unsigned long long want = __ballot(valid);
-    if (want == 0) return;
-    // groups with nothing to do redo the work of one that has (well-defined data -- their own interface operators were
-    // not formed -- and no stores)
-    const int src = __ffsll((long long)want) - 1;
-    const int cm_w = __shfl((int)cm, src, 64);
-    if (!valid) cm = cm_w;
-  }
-  const int m = (int)(cm % d.M), c = (int)(cm / d.M);
-  const int L = d.L, Lm1 = L - 1;
-  double* A_ = sA[grp];
-  double* B_ = sB[grp];
-  double* v0 = sV[grp][0];
-  double* v1 = sV[grp][1];
-  double* v2 = sV[grp][2];
-  double* v3 = sV[grp][3];
-  const double* Ym = d.Ym + cm * L * NP * NP;
-  const double* Am = d.Am + cm * L * NP * NP;
-  const double* kk = d.kk + cm * L * NP;
-  const double rTj = 1.0 / d.T[j];  // row scaling of G: Gp = (Y - A/k)/T, Gm = (Y + A/k)/T
-  const double* Ek = d.Ek + cm * L * NP;
-  const double* Bv = d.Bv + cm * L * Q;
-  const double* ts0 = d.taus0 + (long)c * (L + 1);
-  const double* dq = d.dq + (long)c * L * d.Ns * Q;
-  double* wsb = d.Fws + cm * Lm1 * Ws<NP>::SLOT;
-  double* coef = d.coef + cm * L * Q;
-  const int mg = d.m0 + d.mstep * m;  // the Fourier mode this local index stands for (mode shards)
-  const bool iso = d.Ns > 0 && mg == 0;
-  const bool beam = d.beam != 0;
-  const double mu0 = beam ? d.mu0[c] : 1.0;
-  // thermal particular solution of layer l at one of the layer's own boundaries (top / bottom), streams idx in [0, 2 NP): the values
-  // the eigen kernel left in vb (it holds the polynomial coefficients about the layer's top, rtd_dd.h) -- no polynomial is evaluated here
-  const double* vbp = d.vb + (long)c * L * 4 * NP;
-  auto vedge = [&](int l, bool bottom, int idx) { return vbp[((long)l * 4 + (bottom ? 2 : 0)) * NP + idx]; };
-
-  // carry rows, one per lane: Ta C- + Tb C+ = t.  Top boundary (down-streams at tau = 0) (:161-179, :284-285)
-  double ta_regs[ROWS_IN_LDS ? 1 : NP], tb_regs[ROWS_IN_LDS ? 1 : NP], tt;
-  auto&& ta = pick_row<ROWS_IN_LDS>(ta_regs, sR + j * LDR);
-  auto&& tb = pick_row<ROWS_IN_LDS>(tb_regs, sR + j * LDR + NP);
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const double yv = Ym[j * NP + k], av = Am[j * NP + k] / kk[k];
-    ta[k] = (yv + av) * rTj;          // Gm_0
-    tb[k] = (yv - av) * rTj * Ek[k];  // Gp_0 E_0
-  }
-  tt = d.bneg[cm * NP + j];
-  if (beam) tt -= Bv[NP + j];
-  if (iso) tt -= dq[NP + j];
-
-  int pc = -1;
-  for (int l = 0; l < L; ++l) {
-    pc = -1;
-    if constexpr (ROWS_IN_LDS) {
-      sR[j * LDR + 2 * NP] = tt;
-      gj_rows_in_lds(sR, LDR, j, NP, 2 * NP + 1, pc);
-      tt = sR[j * LDR + 2 * NP];
-    } else {
-      GjStep<NP, NP, 0>::run(ta, tb, tt, pc, grp);  // lane now holds row pc of S = Ta^-1 Tb and s[pc]
-    }
-    // a chain that has gone NaN (failed eigen stage of its mode) finds no pivots: its lanes keep their own row index, so
-    // that what they write below stays inside their group's LDS and workspace (the other chains of the wavefront are
-    // other modes and other columns); the NaN coefficients raise RTD_ST_BC for this chain's mode at the end
-    if (pc < 0) pc = j;
-    if (l == Lm1) break;
-    double* ws = wsb + (long)l * Ws<NP>::SLOT;
-    __syncthreads();
-    {  // stage Wq, Wp of this interface in LDS (coalesced rows); store S row and s for the backward sweep
-      if constexpr (!ROWS_IN_LDS) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-          A_[i * LD + j] = ws[Ws<NP>::WQ + i * NP + j];
-          B_[i * LD + j] = ws[Ws<NP>::WP + i * NP + j];
-        }
-      }
-      v0[j] = ws[Ws<NP>::RB + j];
-      v1[j] = Ek[(l + 1) * NP + j];
-      if (valid) {
-#pragma unroll
-        for (int k = 0; k < NP; ++k) ws[Ws<NP>::S + pc * NP + k] = tb[k];
-        ws[Ws<NP>::SV + pc] = tt;
-      }
-    }
-    __syncthreads();
-    const double Er = Ek[l * NP + pc];
-    double srb = 0.0;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) srb += tb[k] * v0[k];  // (S rho_b)[pc]
-    const double tnew = ws[Ws<NP>::RT + pc] - Er * (tt - srb);
-    if constexpr (ROWS_IN_LDS) {
-      // the S row into registers once (the rows in LDS may alias each other for the compiler), eight columns at a time
-      double srow[NP];
-#pragma unroll
-      for (int k = 0; k < NP; ++k) srow[k] = tb[k];
-      for (int c0 = 0; c0 < NP; c0 += 8) {
-        double swq[8] = {}, swp[8] = {};
-#pragma unroll
-        for (int k = 0; k < NP; ++k)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            swq[e] += srow[k] * ws[Ws<NP>::WQ + k * NP + c0 + e];  // wave-uniform addresses: scalar loads
-            swp[e] += srow[k] * ws[Ws<NP>::WP + k * NP + c0 + e];
-          }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          ta[c0 + e] = -(Er * swq[e] + ws[Ws<NP>::WP + pc * NP + c0 + e]);
-          tb[c0 + e] = -(Er * swp[e] + ws[Ws<NP>::WQ + pc * NP + c0 + e]) * v1[c0 + e];  // (srow keeps the inputs)
-        }
-      }
-    } else {
-    double nbuf[NP];
-#pragma unroll
-    for (int cc = 0; cc < NP; ++cc) {
-      double swq = 0.0, swp = 0.0;
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        swq += tb[k] * A_[k * LD + cc];
-        swp += tb[k] * B_[k * LD + cc];
-      }
-      ta[cc] = -(Er * swq + B_[pc * LD + cc]);           // Ta' = -(E S Wq + Wp)
-      nbuf[cc] = -(Er * swp + A_[pc * LD + cc]) * v1[cc];  // Tb' = -(E S Wp + Wq) E'  (tb is still an input)
-      RTD_FENCE();
-    }
-#pragma unroll
-    for (int k = 0; k < NP; ++k) tb[k] = nbuf[k];
-    }
-    tt = tnew;
-  }
-
-  // ---- bottom boundary (up-streams at tau_L) (:208-232, :248-254, :288-293):  Ba C- + Bb C+ = br,
-  //      with C- = s - S C+  ->  (Bb - Ba S) C+ = br - Ba s.
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NP; ++k)
-    if constexpr (!ROWS_IN_LDS) A_[pc * LD + k] = tb[k];  // S at its true row index
-  int* lane_of_row = reinterpret_cast<int*>(v3);  // rows in LDS: row r of S is the Tb part of lane lane_of_row[r]
-  if constexpr (ROWS_IN_LDS) lane_of_row[pc] = j;
-  v0[pc] = tt;                                            // s
-  __syncthreads();
-  {
-    const int l = Lm1;
-    const double* ymL = Ym + (long)l * NP * NP;
-    const double* amL = Am + (long)l * NP * NP;
-    const double* kl = kk + (long)l * NP;
-    const double att = beam ? exp(-ts0[L] / mu0) : 0.0;
-    // Ba = Gp - R Gm, Bb = Gm - R Gp  built from  P = (I - R) Y / T-rows and  Qd = (I + R) A / (k T-rows):
-    //   Gp = P0 - Q0, Gm = P0 + Q0 with P0 = Y/T, Q0 = A/(kT)  =>  Ba = (P0 - R P0) - (Q0 + R Q0), Bb = (P0 - R P0) + (Q0 + R Q0)
-    double pa[NP], qa[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      pa[k] = ymL[j * NP + k] * rTj;
-      qa[k] = amL[j * NP + k] * rTj;
-    }
-    double br = d.bpos[cm * NP + j];
-    if (mg < d.NBDRF) {
-      const double delta = (mg == 0) ? 2.0 : 1.0;
-      const double* qt = d.bdrfq + (((long)c * d.NBDRF + mg) * NP + j) * NP;
-      double rbm = 0.0, rvm = 0.0;
-      for (int j2 = 0; j2 < NP; ++j2) {
-        const double Rij = delta * qt[j2] * d.mu[j2] * d.w[j2] / d.T[j2];  // R = (1 + delta_m0) q (mu w), times 1/T_j2
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-          pa[k] -= Rij * ymL[j2 * NP + k];
-          qa[k] += Rij * amL[j2 * NP + k];
-        }
-        const double Rraw = Rij * d.T[j2];
-        if (beam) rbm += Rraw * Bv[l * Q + NP + j2];
-        if (iso) rvm += Rraw * vedge(l, true, NP + j2);
-      }
-      if (beam) {
-        const double Xs = mu0 * d.I0[c] / M_PI * d.bdrfq0[((long)c * d.NBDRF + mg) * NP + j];
-        br += (Xs + rbm - Bv[l * Q + j]) * att;
-      }
-      if (iso) br += rvm - vedge(l, true, j);
-    } else {
-      if (beam) br -= Bv[l * Q + j] * att;
-      if (iso) br -= vedge(l, true, j);
-    }
-    double ba[NP], bb[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const double qk = qa[k] / kl[k];
-      ba[k] = pa[k] - qk;
-      bb[k] = pa[k] + qk;
-    }
-#pragma unroll
-    for (int k = 0; k < NP; ++k) ba[k] *= Ek[l * NP + k];
-    // am = Bb - Ba S,  bvec = br - Ba s
-    double am[NP], dummy[1] = {0.0};
-#pragma unroll
-    for (int cc = 0; cc < NP; ++cc) {
-      double a = bb[cc];
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        if constexpr (ROWS_IN_LDS) a -= ba[k] * sR[lane_of_row[k] * LDR + NP + cc];
-        else a -= ba[k] * A_[k * LD + cc];
-      }
-      am[cc] = a;
-      RTD_FENCE();
-    }
-    double bvec = br;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) bvec -= ba[k] * v0[k];
-    int pc2 = -1;
-    if constexpr (ROWS_IN_LDS) {  // (the Ta part of the rows is free; the S rows stay where they are)
-#pragma unroll
-      for (int k = 0; k < NP; ++k) ta[k] = am[k];
-      sR[j * LDR + 2 * NP + 1] = bvec;
-      gj_rows_in_lds(sR, LDR, j, 2 * NP + 1, 2 * NP + 2, pc2);
-      bvec = sR[j * LDR + 2 * NP + 1];
-    } else {
-      GjStep<NP, 1, 0>::run(am, dummy, bvec, pc2, grp);  // lane holds C+[pc2]
-    }
-    if (pc2 < 0) pc2 = j;  // (NaN chain, as above)
-    v1[pc2] = bvec;
-    __syncthreads();
-    double cmin = tt;  // C-[pc] = s[pc] - S[pc][:] C+
-#pragma unroll
-    for (int k = 0; k < NP; ++k) cmin -= tb[k] * v1[k];
-    v2[pc] = cmin;
-    __syncthreads();
-    if (valid) {
-      coef[(long)l * Q + j] = v2[j];
-      coef[(long)l * Q + NP + j] = v1[j];
-      // singular system (the reference's solve_banded / solve raises LinAlgError, :326-333, :383)
-      if (!(fabs(v2[j]) + fabs(v1[j]) < 1e300)) rtd_raise(d, RTD_ST_BC, mg, c);
-    }
-  }
-  // ---- backward sweep: C+_l = Wq C-' + Wp E' C+' + rho_b ;  C-_l = s - S C+_l
-  if constexpr (NP == 16) {
-    // lane j keeps C-_l[j], C+_l[j]; the other lanes' values arrive by DPP row broadcasts (no LDS, no barriers)
-    double cmj = v2[j], cpj = v1[j];
-    for (int l = Lm1 - 1; l >= 0; --l) {
-      const double* ws = wsb + (long)l * Ws<NP>::SLOT;
-      double wq[NP], wp[NP], sr[NP];
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        wq[k] = ws[Ws<NP>::WQ + j * NP + k];
-        wp[k] = ws[Ws<NP>::WP + j * NP + k];
-        sr[k] = ws[Ws<NP>::S + j * NP + k];
-      }
-      double cp = ws[Ws<NP>::RB + j];
-      double cmin = ws[Ws<NP>::SV + j];
-      const double ecp = Ek[(l + 1) * NP + j] * cpj;  // E'_j C+'_j
-      static_for<0, NP>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        cp += wq[k] * bcast16<k>(cmj) + wp[k] * bcast16<k>(ecp);
-      });
-      static_for<0, NP>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        cmin -= sr[k] * bcast16<k>(cp);
-      });
-      cmj = cmin;
-      cpj = cp;
-      if (valid) {
-        coef[(long)l * Q + j] = cmin;
-        coef[(long)l * Q + NP + j] = cp;
-      }
-    }
-  } else {
-    for (int l = Lm1 - 1; l >= 0; --l) {
-      const double* ws = wsb + (long)l * Ws<NP>::SLOT;
-      double cp = ws[Ws<NP>::RB + j];
-#pragma unroll 4
-      for (int k = 0; k < NP; ++k)
-        cp += ws[Ws<NP>::WQ + j * NP + k] * v2[k] + ws[Ws<NP>::WP + j * NP + k] * (Ek[(l + 1) * NP + k] * v1[k]);
-      v3[j] = cp;
-      __syncthreads();
-      double cmin = ws[Ws<NP>::SV + j];
-#pragma unroll 4
-      for (int k = 0; k < NP; ++k) cmin -= ws[Ws<NP>::S + j * NP + k] * v3[k];
-      __syncthreads();
-      v1[j] = cp;
-      v2[j] = cmin;
-      if (valid) {
-        coef[(long)l * Q + j] = cmin;
-        coef[(long)l * Q + NP + j] = cp;
-      }
-      __syncthreads();
-    }
-  }
-}
-
+#include "rtd_bc_tile_common.h"
 
 // ------------------------------------------------------------------------------------------------
 // Fused boundary-condition kernel, NP = 16: ONE wavefront per (column, mode) does the interface operators, the
@@ -524,15 +41,14 @@ __global__ __launch_bounds__(64, (NP <= 8 ? RTD_SWEEP_WAVES : (NP == 16 ? 2 : 1)
 // Y = I, so the recursion is carried in transposed form:
 //      H = S^T ,   Ta'^T = -(Wq^T (H E) + Wp^T) ,   Tb'^T = -E' (Wp^T (H E) + Wq^T) ,   H' = Tb'^T Ta'^-T
 // (column-pivoted Gauss-Jordan on the stacked rows [Ta'^T ; Tb'^T ; t'^T]: columns = lanes, the same elimination
-// as the two-kernel path seen through a transpose).  W and W^T come from the eigen stage's Y, A straight from HBM
+// as the row-per-lane kernels' (rtd_bc_rows.hip) seen through a transpose).  W and W^T come from the eigen stage's Y, A straight from HBM
 // (each layer is read once per direction); nothing but H_l, s_l and rho_b is stored for the backward sweep, which
 // applies W through its factors:  Wq x + Wp y = [A_l^T Y' (x + y) + k_l Y_l^T A' ((y - x)/k')] / 2.
-// Against the two-kernel path this removes the Wp/Wq round trip through HBM (about 40 % of the stage's traffic).
+// Against that two-kernel path this removes the Wp/Wq round trip through HBM (about 40 % of the stage's traffic).
 // ------------------------------------------------------------------------------------------------
 #ifndef RTD_BCF_WIN
 #define RTD_BCF_WIN 20  // layers of small vectors resident in LDS (12.6 KB per wavefront with the save area: 12 per CU)
 #endif
-#include "rtd_bc_tile_common.h"
 
 // Speculative, branch-free form of the same elimination with the diagonal as pivot at every step: straight-line
 // code (the 16 steps schedule into each other), no pivot search.  A step whose diagonal candidate is more than a
@@ -1326,42 +842,22 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
   if (!(fabs(cminus) + fabs(cplus) < 1e300)) rtd_raise(d, RTD_ST_BC, mg, c);
 }
 
-// The row-per-lane pair as a boundary-condition stage of its own (RTD_SMALL_SPLIT, RTD_BC_WIDE_V1): every chain.
-// part 0: interface operators (all interfaces in parallel), 1: carry recursion / bottom BC / backward sweep
-template <int NP>
-void launch_rows(const RtdDev& d, hipStream_t s, int part) {
-  constexpr int GPW = 64 / NP;
-  const long nif = (long)d.C * d.M * (d.L - 1);
-  const int* none = nullptr;
-  if (part == 0 && nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<NP>, dim3((unsigned)((nif + GPW - 1) / GPW)), dim3(64), 0, s, d, none);
-  if (part == 1) hipLaunchKernelGGL(rtd_sweep_kernel<NP>, dim3((unsigned)(((long)d.C * d.M + GPW - 1) / GPW)), dim3(64), 0, s, d, none);
-}
-
 }  // namespace
-
-bool rtd_small_split() {  // RTD_SMALL_SPLIT: 2 ... 16 streams through rtd_iface_kernel + rtd_sweep_kernel + rtd_eval_kernel (A/B, tests)
-  static const bool v = getenv("RTD_SMALL_SPLIT") != nullptr;
-  return v;
-}
 
 bool rtd_bc_fuses_eval(const RtdDev& d) {
   // the fused kernels -- rtd_bc_small_kernel (NP <= 8), rtd_bc_mfma_kernel (16) and rtd_bc_tile2_kernel (32 streams per hemisphere) --
   // write u^m at the interfaces themselves; a window in which the 64-stream kernel handed a chain to the row-per-lane kernels
-  // (d.split_any) is evaluated by the evaluation kernel instead (rtd_launch_eval)
-  return d.NP == 16 || d.NP == 32 || (d.NP <= 8 && !rtd_small_split());
+  // (d.split_any) is evaluated by the evaluation kernel instead (rtd_launch_eval); the 66 ... 128-stream kernels (NP = 64) do not
+  return d.NP <= 32;
 }
 
 void rtd_launch_bc(const RtdDev& d, hipStream_t s, int part) {
   // the fused kernels run in one of the two parts and leave the other empty
   const long nch = (long)d.C * d.M;
   switch (d.NP) {
-    case 4:  // 2 ... 16 streams: one fused kernel unless RTD_SMALL_SPLIT asks for the separate ones
-      if (rtd_small_split()) launch_rows<4>(d, s, part);
-      else if (part == 1) rtd_launch_bc_small(d, s);
-      break;
+    case 4:  // 2 ... 16 streams
     case 8:
-      if (rtd_small_split()) launch_rows<8>(d, s, part);
-      else if (part == 1) rtd_launch_bc_small(d, s);
+      if (part == 1) rtd_launch_bc_small(d, s);
       break;
     case 16:  // 18 ... 32 streams
       if (part == 1) hipLaunchKernelGGL(rtd_bc_mfma_kernel, dim3((unsigned)nch), dim3(64), 0, s, d);
@@ -1373,17 +869,12 @@ void rtd_launch_bc(const RtdDev& d, hipStream_t s, int part) {
         (void)hipMemsetAsync(d.split_any, 0, sizeof(int), s);
         rtd_launch_bc_tile2(d, s);
       } else {
-        const long nif = nch * (d.L - 1);
-        if (nif > 0) hipLaunchKernelGGL(rtd_iface_kernel<32>, dim3((unsigned)((nif + 1) / 2)), dim3(64), 0, s, d, (const int*)d.need_split);
-        hipLaunchKernelGGL(rtd_sweep_kernel<32>, dim3((unsigned)((nch + 1) / 2)), dim3(64), 0, s, d, (const int*)d.need_split);
+        rtd_launch_bc_rows(d, s);
       }
       break;
-    case 64: {  // 66 ... 128 streams: four wavefronts per chain (rtd_bc_wide.hip) unless RTD_BC_WIDE_V1 asks for the row-per-lane kernels
-      static const bool wide_v1 = getenv("RTD_BC_WIDE_V1") != nullptr;
-      if (wide_v1) launch_rows<64>(d, s, part);
-      else rtd_launch_bc_wide(d, s, part);
+    case 64:  // 66 ... 128 streams: four wavefronts per chain
+      rtd_launch_bc_wide(d, s, part);
       break;
-    }
     default: break;
   }
 }

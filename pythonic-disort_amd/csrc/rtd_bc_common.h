@@ -1,4 +1,4 @@
-// rtd_bc_common.h -- helpers shared by the boundary-condition kernels (rtd_bc.hip, rtd_bc_small.hip): cross-lane moves, the
+// rtd_bc_common.h -- helpers shared by the boundary-condition kernels (rtd_bc*.hip): cross-lane moves, the
 // workspace layout of an interface and the row-per-lane Gauss-Jordan step.  Included inside each file's anonymous namespace.
 #pragma once
 
@@ -6,31 +6,16 @@
 #ifndef RTD_GJ_BATCH
 #define RTD_GJ_BATCH 3  /* cross-lane fetches in flight per batch - 1 (power of two minus one) */
 #endif
-#ifndef RTD_SWEEP_WAVES
-#define RTD_SWEEP_WAVES 3
-#endif
 
 template <int MASK>
 __device__ __forceinline__ double xor_lane(double v) {
-  if constexpr (MASK >= 32) return __shfl_xor(v, MASK, 64);  // across the halves of the wavefront: ds_bpermute (128 streams only)
+  static_assert(MASK < 32, "ds_swizzle stays inside a half of the wavefront");
   constexpr int pat = (MASK << 10) | 0x1F;
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __builtin_amdgcn_ds_swizzle(lo, pat);
   hi = __builtin_amdgcn_ds_swizzle(hi, pat);
   return __hiloint2double(hi, lo);
 }
-
-template <int NP>
-__device__ __forceinline__ double group_max(double v) {
-  if (NP > 1) v = fmax(v, xor_lane<1>(v));
-  if (NP > 2) v = fmax(v, xor_lane<2>(v));
-  if (NP > 4) v = fmax(v, xor_lane<4>(v));
-  if (NP > 8) v = fmax(v, xor_lane<8>(v));
-  if (NP > 16) v = fmax(v, xor_lane<16>(v));
-  if (NP > 32) v = fmax(v, xor_lane<32>(v));
-  return v;
-}
-
 
 // max over the NP lanes of a group for non-negative f32 keys, with DPP row operations (no LDS crossbar):
 // xor-1 and xor-2 quad permutes, row_half_mirror, row_mirror; one v_max_f32 each.
@@ -49,7 +34,6 @@ __device__ __forceinline__ float group_max_key(float v) {
     const int o = __builtin_amdgcn_ds_swizzle(__float_as_int(v), (16 << 10) | 0x1F);
     v = fmaxf(v, __int_as_float(o));
   }
-  if (NP > 32) v = fmaxf(v, __shfl_xor(v, 32, 64));
   return v;
 }
 
@@ -96,12 +80,6 @@ template <int K>
 __device__ __forceinline__ double bcast8(double v) {
   return __hiloint2double(bcast8_i<K>(__double2hiint(v)), bcast8_i<K>(__double2loint(v)));
 }
-// lane K of the caller's NP-lane group for NP = 8 or 16
-template <int NP, int K>
-__device__ __forceinline__ double bcast_grp(double v) {
-  if constexpr (NP == 16) return bcast16<K>(v);
-  else return bcast8<K>(v);
-}
 
 // v[c] -= f * (lane K of the caller's 8-lane group's v[c]) for c in [C0, C1), ONE half of a 16-lane DPP row per instruction: the DP
 // ALU's DPP form is the row broadcast, so lane K of the row serves the banks of its lower eight lanes (HI = false) and lane 8 + K
@@ -136,6 +114,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 // that owned pivot column `pc` holds row pc of A^-1 B in bm[] and (A^-1 b)[pc] in bv.
 template <int NP, int NB, int K>
 struct GjStep {
+  static_assert(NP == 4 || NP == 8 || NP == 32, "group sizes in use: rtd_bc_small.hip, rtd_bc_rows.hip");
   static __device__ __forceinline__ void run(double (&am)[NP], double (&bm)[NB], double& bv, int& pc, const int grp) {
     // pivot search on f32 keys (a pivot within 2^-24 of the largest candidate is as good as the largest)
     const float key = (pc < 0) ? fabsf((float)am[K]) : -1.0f;
@@ -144,15 +123,13 @@ struct GjStep {
     double f, rp;
     bool isp;
     bool fast = false;
-    if constexpr (NP == 16 || NP == 8) {
+    if constexpr (NP == 8) {
       // threshold pivoting: when the diagonal candidate (lane K, still unused) is within a factor 4 of the largest
       // candidate of its group, it is taken as the pivot: the source lane is then a compile-time
       // constant and the pivot row travels by DPP row broadcasts (VALU) instead of ds_bpermute (LDS crossbar, the
       // pipe that bounds this kernel).  ~95 % of the steps of real atmospheres qualify; the others take the fully
       // pivoted path below.  Growth is bounded as in partial pivoting with threshold 1/4.
-      int kd;
-      if constexpr (NP == 16) kd = __builtin_amdgcn_update_dpp(0, __float_as_int(key), 0x150 + K, 0xF, 0xF, true);
-      else kd = bcast8_i<K>(__float_as_int(key));  // (NP = 8: two groups per DPP row, see bcast8)
+      const int kd = bcast8_i<K>(__float_as_int(key));  // (two groups per DPP row, see bcast8)
       // (decided per group, not per wavefront: a chain's arithmetic must not depend on which chains share its wavefront -- a
       //  windowed plan groups them differently and has to return the same bits; a wavefront whose groups all qualify skips
       //  the pivoted branch altogether)
@@ -160,10 +137,10 @@ struct GjStep {
     }
     if (fast) {
       isp = (j == K);
-      const double piv = bcast_grp<NP, K>(am[K]);
+      const double piv = bcast8<K>(am[K]);
       rp = fast_rcp(piv);
       f = isp ? 0.0 : am[K] * rp;
-      if constexpr (NP == 8) {
+      if constexpr (NP == 8) {  // (`fast` is only ever set there)
         // (see FmacBank8: two bank-masked v_fmac_f64_dpp per register; all first halves, then all second halves)
         FmacBank8<K, false, K + 1, NP, NP>::run(am, f);
         FmacBank8<K, false, 0, NB, NB>::run(bm, f);
@@ -171,20 +148,10 @@ struct GjStep {
         FmacBank8<K, true, K + 1, NP, NP>::run(am, f);
         FmacBank8<K, true, 0, NB, NB>::run(bm, f);
         asm volatile("v_fmac_f64_dpp %0, -%0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xc\n\ts_nop 1" : "+v"(bv) : "v"(f), "n"(8 + K));
-      } else {
-      static_for<K + 1, NP>([&](auto cc) {
-        constexpr int c = decltype(cc)::value;
-        am[c] -= f * bcast_grp<NP, K>(am[c]);
-      });
-      static_for<0, NB>([&](auto cc) {
-        constexpr int c = decltype(cc)::value;
-        bm[c] -= f * bcast_grp<NP, K>(bm[c]);
-      });
-      bv -= f * bcast_grp<NP, K>(bv);
       }
     } else {
       const unsigned long long bal = __ballot(key == kmax);
-      const unsigned long long bits = NP == 64 ? bal : (bal >> (grp * NP)) & ((1ull << (NP & 63)) - 1);
+      const unsigned long long bits = (bal >> (grp * NP)) & ((1ull << NP) - 1);
       const int src = __ffsll((long long)bits) - 1;  // pivot lane of this group
       isp = (j == src);
       const int addr = (grp * NP + src) << 2;

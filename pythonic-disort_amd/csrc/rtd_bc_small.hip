@@ -14,7 +14,7 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // Fused boundary-condition kernel for 2 ... 16 streams (NP = 4, 8; round 4): what rtd_iface_kernel + rtd_sweep_kernel +
 // the evaluation kernel did in three launches with Wp, Wq, S through HBM, in one.  NP lanes per (column, mode) chain, 64/NP
-// chains per wavefront, lane j = row j of the carry system (the elimination is GjStep, as in rtd_sweep_kernel).  Measured on
+// chains per wavefront, lane j = row j of the carry system (the elimination is GjStep, as in rtd_sweep_kernel, rtd_bc_rows.hip).  Measured on
 // cfg3 (8 layers, 16 streams, 1 024 columns; profiles/archive/r04_small_stream_path.json): the interface kernel was HBM-bound (310 MB
 // in 65 us), the sweep kernel a chain of memory latencies (every layer waited for Wp, Wq right after asking for them; 2
 // wavefronts per SIMD: 121 us whatever the batch), the evaluation kernel read Y, A of every point's layer again (92 us).
@@ -28,8 +28,7 @@ namespace {
 //     u_up = (p + q)/T + particular, u_down = (p - q)/T + particular -- the interface evaluation costs two extra row sums per
 //     chain (tau = 0 and tau_L); only S_l, s_l, rho_b go through HBM (stored after the loads of an iteration were issued);
 //   * run-path points that are the layer interfaces are written as u^m [c][m][t][2 NP] for rtd_fourier_kernel (d.um).
-// The separate kernels remain: behind RTD_SMALL_SPLIT (A/B, and the suite runs under it), behind RTD_BC_WIDE_V1 for 66 ... 128
-// streams, and as the 64-stream kernel's last resort.
+// The separate kernels remain as the 64-stream kernel's last resort only (rtd_bc_rows.hip, 32 lanes per chain).
 // ------------------------------------------------------------------------------------------------
 // Diagnostic build (-DRTD_BCS_STAMPS, never shipped): lane 0 of one wavefront records s_memtime at the phase boundaries of the
 // forward and backward loops and prints the differences (cycles).

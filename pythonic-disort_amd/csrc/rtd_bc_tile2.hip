@@ -14,7 +14,7 @@
 //   nothing hides the dependency stalls: VALU issue 30 % + matrix pipe 22 % of the SIMD cycles, measured on this kernel's
 //   predecessor, profiles/archive/r03_pmc_traffic_cfg5.json; that kernel, its 472 VGPRs and its LDS redo are in HISTORY.md.)
 //   A chain that still cannot be solved (singular carry block) raises its flag in need_split and leaves; the row-per-lane
-//   kernels of rtd_bc.hip (partial pivoting) solve the flagged chains afterwards.
+//   kernels of rtd_bc_rows.hip (partial pivoting) solve the flagged chains afterwards.
 //   End of round 5 (profiles/r05_bc_tile2_phases.txt): what the carry across an interface reads -- Y, A of the layer below and the
 //   interface's vectors -- arrives by LDS-DMA (global_load_lds_dwordx4: no registers, no wait) while the elimination above runs;
 //   the carry's only wait finds requests that are an elimination old, H and s are stored BEHIND it (loads, stores and the DMA share

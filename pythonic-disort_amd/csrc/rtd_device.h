@@ -51,7 +51,7 @@ struct RtdDev {
   double* vb;         // [C][L][4][NP]  the thermal particular solution v_l at the layer's own boundaries: up- and down-streams at its
                       //                top, then at its bottom (mode 0 only; read by rtd_bc_small_kernel instead of the polynomials)
   double* Ek;         // [C][M][L][NP]  exp(-k dtau*_l): the Stamnes-Conklin scaling factors
-  double* Fws;  // BC workspace: [C][M][L-1][4 NP^2]: Wp, Wq, S, rho_t, rho_b, s per interface (rtd_bc.hip)
+  double* Fws;  // BC workspace: [C][M][L-1][4 NP^2]: Wp, Wq, S, rho_t, rho_b, s per interface (rtd_bc_common.h: Ws)
   // Fused evaluation (rtd_bc_mfma_kernel): when the evaluation points are the layer interfaces [0, tau_arr] the backward
   // sweep of the boundary-condition kernel forms the Fourier modes of the intensity there itself -- Y_l, A_l and the
   // coefficients are in its registers, the exponentials are E_l or 1 -- and the evaluation kernel only sums over the modes.
@@ -121,8 +121,8 @@ void rtd_launch_eig(const RtdDev& d, hipStream_t s, int part);  // the fused eig
 void rtd_launch_bc(const RtdDev& d, hipStream_t s, int part);   // 0 iface, 1 sweep
 void rtd_launch_bc_small(const RtdDev& d, hipStream_t s);  // rtd_bc_small.hip: the fused kernel of the 2 ... 16-stream path
 void rtd_launch_bc_tile2(const RtdDev& d, hipStream_t s);  // rtd_bc_tile2.hip: the lean 64-stream kernel (two wavefronts per SIMD)
+void rtd_launch_bc_rows(const RtdDev& d, hipStream_t s);  // rtd_bc_rows.hip: the chains flagged in d.need_split again, with partial pivoting (32 lanes per chain)
 void rtd_launch_bc_wide(const RtdDev& d, hipStream_t s, int part);  // rtd_bc_wide.hip: 66 ... 128 streams, four wavefronts per chain (0 iface, 1 sweep)
-bool rtd_small_split();  // RTD_SMALL_SPLIT is set: NP <= 8 takes the separate interface / sweep / evaluation kernels
 bool rtd_bc_fuses_eval(const RtdDev& d);  // the boundary-condition kernel chosen for d can fill d.um
 void rtd_launch_eval(const RtdDev& d, const RtdEval& e, hipStream_t s);
 void rtd_launch_nt_tables(const RtdDev& d, const RtdNt& nt, hipStream_t s);

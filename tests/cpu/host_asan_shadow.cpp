@@ -127,8 +127,7 @@ void rtd_launch_eig(const RtdDev& d, hipStream_t, int part) {
   if (part == 1) eig_shadow(d);
 }
 
-bool rtd_small_split() { return false; }
-bool rtd_bc_fuses_eval(const RtdDev& d) { return d.NP == 16 || d.NP == 32 || d.NP <= 8; }
+bool rtd_bc_fuses_eval(const RtdDev& d) { return d.NP <= 32; }
 
 void rtd_launch_bc(const RtdDev& d, hipStream_t, int part) {
   if (part != 1) return;
@@ -146,6 +145,7 @@ void rtd_launch_bc(const RtdDev& d, hipStream_t, int part) {
 }
 void rtd_launch_bc_small(const RtdDev& d, hipStream_t s) { rtd_launch_bc(d, s, 1); }
 void rtd_launch_bc_tile2(const RtdDev& d, hipStream_t s) { rtd_launch_bc(d, s, 1); }
+void rtd_launch_bc_rows(const RtdDev& d, hipStream_t s) { rtd_launch_bc(d, s, 1); }
 void rtd_launch_bc_wide(const RtdDev& d, hipStream_t s, int part) { rtd_launch_bc(d, s, part); }
 
 void rtd_launch_eval(const RtdDev& d, const RtdEval& e, hipStream_t) {

@@ -675,8 +675,8 @@ def test_baseline_literal_configs(amd, name):
 @pytest.mark.parametrize("name", ["q72", "q96", "q128"])
 def test_beyond_64_streams_vs_reference(amd, name):
     """72 / 96 / 128 streams -- the reference has no cap on NQuad (pydisort.py:258-264); these sizes run on the NP = 64 instances
-    (one eigenproblem per wavefront; a boundary-condition chain per workgroup of four wavefronts, csrc/rtd_bc_wide.hip; one chain per
-    wavefront on the row-per-lane kernels under RTD_BC_WIDE_V1) -- against the reference's own outputs
+    (one eigenproblem per wavefront; a boundary-condition chain per workgroup of four wavefronts, csrc/rtd_bc_wide.hip) -- against
+    the reference's own outputs
     (tests/golden/synth/q*.npz, make_synthetic_goldens.py).  Tolerances (round 6: ten times what is measured, not 1e-7 / 1e-6):
     WIDE_TOL = 1e-8 of the field scale (measured 8e-11 ... 7.3e-10; the reference's float64 algorithm and its restatement in
     oracle/ differ by 3e-10 from each other here), WIDE_PW_TOL = 4e-7 pointwise (measured 3e-10 ... 3.5e-8)."""
@@ -1007,32 +1007,29 @@ def test_fused_bc_kernel_pivoted_path_on_goldens(how):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("switch", ["RTD_EIG_MFMA", "RTD_BC_FORCE_HANDOVER", "RTD_NO_PIPELINE", "RTD_SMALL_SPLIT", "RTD_BC_WIDE_V1"])
+@pytest.mark.parametrize("switch", ["RTD_EIG_MFMA", "RTD_BC_FORCE_HANDOVER", "RTD_NO_PIPELINE"])
 def test_alternative_kernel_paths_stay_correct(switch):
     """The runtime switches that select an alternative path -- RTD_EIG_MFMA=1: the assembly of Pm, Qm as rank-4 MFMA updates
     (32 streams); RTD_BC_FORCE_HANDOVER=1: the tiled (64-stream) kernel hands every third Fourier mode's chain to the pivoted
-    row-per-lane kernels (its last resort for singular carry blocks; the window's fused interface evaluation is then
-    replaced by the evaluation kernel); RTD_NO_PIPELINE=1: the windows of a plan one after the other on one stream instead
-    of the two-stream pipeline; RTD_SMALL_SPLIT=1: 2 ... 16 streams through the separate interface / sweep / evaluation kernels
-    of rounds 1-3 instead of the fused rtd_bc_small_kernel (round 4); RTD_BC_WIDE_V1=1: 66 ... 128 streams through the
-    row-per-lane kernels (one wavefront per chain) instead of the four-wavefronts-per-chain kernels of rtd_bc_wide.hip -- pass the golden replay (it has 40-, 48- and 64-stream cases), the synthetic configs incl.
-    cfg5, the random cases, the windowed plans and the fused-evaluation comparison.  (Round 3 removed the switches whose
-    paths had lost every A/B: RTD_BC_SPLIT at 32 streams, RTD_EIG_V1, RTD_BCF_WAVES3; the kernels that round 4 superseded went
-    the same way later, with their three switches: HISTORY.md.)"""
+    row-per-lane kernels (csrc/rtd_bc_rows.hip: its last resort for singular carry blocks; the window's fused interface
+    evaluation is then replaced by the evaluation kernel); RTD_NO_PIPELINE=1: the windows of a plan one after the other on one
+    stream instead of the two-stream pipeline -- pass the golden replay (it has 40-, 48- and 64-stream cases), the synthetic
+    configs incl. cfg5, the random cases, the windowed plans and the fused-evaluation comparison.  (Round 3 removed the switches
+    whose paths had lost every A/B: RTD_BC_SPLIT at 32 streams, RTD_EIG_V1, RTD_BCF_WAVES3; the kernels that round 4 superseded
+    went the same way later, with their five switches -- the last two ran the row-per-lane kernels as a stage of their own at
+    2 ... 16 and 66 ... 128 streams: HISTORY.md.)"""
     import subprocess
     import sys
     env = dict(os.environ, **{switch: "1"})
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
                         os.path.join(os.path.dirname(__file__), "test_gpu_parity.py"),
                         os.path.join(os.path.dirname(__file__), "test_gpu_random_parity.py"),
-                        "-k", "reference_golden or synthetic_config or random_many or edge_cases or fused_interface or windowed or layer_shards"
-                              + (" or stamnes or cfg3 or random or mode_shards or failed_column or failure_in" if switch == "RTD_SMALL_SPLIT" else "")
-                              + (" or beyond_64 or random_128 or random_many" if switch == "RTD_BC_WIDE_V1" else "")],
+                        "-k", "reference_golden or synthetic_config or random_many or edge_cases or fused_interface or windowed or layer_shards"],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    if switch in ("RTD_EIG_MFMA", "RTD_NO_PIPELINE", "RTD_BC_WIDE_V1"):
+    if switch in ("RTD_EIG_MFMA", "RTD_NO_PIPELINE"):
         # round 6: the retained forms under the switches that change the eigen stage (RTD_EIG_MFMA has its own reading of the lean
-        # form's chunk lists), the window pipeline, or the consumers of the hand-off at 96 streams
+        # form's chunk lists) or the window pipeline
         r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
                             os.path.join(os.path.dirname(__file__), "test_gpu_retained.py"), "-k", "windowed_plan or lean_plan or auto_retention"],
                            env=env, capture_output=True, text=True, timeout=1200)
@@ -1292,6 +1289,51 @@ def test_64_stream_dispatch_and_handover_count(amd, monkeypatch):
             assert err < TOL, (forced, i, err)
             assert err_pw < PW_TOL, (forced, i, err_pw)
         sol.plan.close()
+
+
+@pytest.mark.gpu
+def test_a_failed_column_under_forced_handover_does_not_touch_the_rest(amd, monkeypatch):
+    """The row-per-lane kernels (csrc/rtd_bc_rows.hip) run two chains per wavefront, and a chain that has gone NaN finds no pivots:
+    its lanes keep their own row index, so that what they write stays inside their own group's LDS and workspace.  3 columns x 3
+    layers x 40 streams (padded to NP = 32) x 1 Fourier mode under RTD_BC_FORCE_HANDOVER=1; the middle column fails the way the
+    column of the 72-stream test does (the 41-moment truncation of a g = 0.99 Henyey-Greenstein phase function is not positive,
+    no delta-M: the eigen stage's Cholesky factorisation fails).  One mode is enough: the forced hand-over takes local mode 0 of
+    every column, and it is mode 0 of the middle column that fails -- the LOW byte of its column_status carries RTD_ST_CHOL (the
+    modes m > 0 raise the next byte; at this size every mode of the column fails, mode 0 among them) -- so with
+    pivoted_chains() == 3 every chain went to the pair, the NaN one too, and the sweep kernel's first wavefront holds column 0
+    next to the NaN chain.  In the batch without the failing column the same wavefront holds the two healthy columns: their u, u0
+    and fluxes must be the same bits either way."""
+    NQ, M = 40, 1
+    def column(g):
+        return dict(tau_arr=np.array([0.5, 1.0, 3.0]), omega_arr=np.array([0.8, 0.9, 0.7]),
+                    Leg_coeffs_all=np.stack([0.6 ** np.arange(NQ + 1), g ** np.arange(NQ + 1), 0.5 ** np.arange(NQ + 1)]))
+    good, bad = column(0.9), column(0.99)
+    def batch(cols):
+        n = len(cols)
+        return dict(tau_arr=np.stack([k["tau_arr"] for k in cols]), omega_arr=np.stack([k["omega_arr"] for k in cols]), NQuad=NQ,
+                    Leg_coeffs_all=np.stack([k["Leg_coeffs_all"] for k in cols]), mu0=np.full(n, 0.6), I0=np.full(n, 1.0),
+                    phi0=np.full(n, 0.0), NFourier=M, numeric_errors="nan")
+    tau, phi = np.array([0.0, 0.7, 3.0]), np.array([0.0, 1.0])
+    monkeypatch.setenv("RTD_BC_FORCE_HANDOVER", "1")
+    out = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for cols in ([good, bad, good], [good, good]):
+            _, sol = amd.pydisort_batch(**batch(cols))
+            taub = np.tile(tau, (len(cols), 1))
+            fd = sol.flux_down(taub)
+            out.append(dict(u=sol.u(taub, phi), u0=sol.u0(taub), flux_up=sol.flux_up(taub), flux_down_diffuse=fd[0], flux_down_direct=fd[1],
+                            status=sol.plan.column_status().copy(), chains=sol.plan.pivoted_chains()))
+            sol.plan.close()
+    mixed, healthy = out
+    assert np.array_equal(mixed["status"] != 0, [False, True, False]), mixed["status"]
+    assert int(mixed["status"][1]) & 4, hex(int(mixed["status"][1]))  # RTD_ST_CHOL in the low byte: raised by mode 0
+    assert mixed["chains"] == 3 and healthy["chains"] == 2, (mixed["chains"], healthy["chains"])
+    assert not np.any(healthy["status"])
+    assert np.all(np.isnan(mixed["u"][1]))
+    for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct"):
+        assert np.all(np.isfinite(healthy[k])), k
+        assert np.array_equal(mixed[k][[0, 2]], healthy[k]), k
 
 
 @pytest.mark.gpu
