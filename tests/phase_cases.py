@@ -14,7 +14,17 @@ No column with an omega > 1 - 1e-5 layer has a thermal source (tests/test_gpu_ra
 test_thermal_polynomial_in_a_near_conservative_thin_layer_is_as_good_as_the_reference says why no tolerance exists there).
 
 Stream counts: 6, 14, 30, 62, 126 (one pair short of the padded widths 4 / 8 / 16 / 32 / 64 per hemisphere) carry all six columns;
-8, 16, 32, 64, 128 carry c5 only.  Three layers up to 64 streams, two at 126 / 128, where c1 drops its last layer and c5 its first.
+8, 16, 32, 64, 128 carry c5 only.  PADDED carries all six as well: 10, 18, 34, 98 are the most-padded ends of the widths 8 / 16 / 32 /
+64 (one pair past the next smaller width), and 66, 94, 96 the 48-lane class of the wide boundary-condition kernels (66 ... 96 streams)
+at its most-padded end, one pair short and full; each takes the g, g1, g2, b of the next smaller count of FULL.  2 and 4 streams are
+left out: c3 and c4 cannot be stated there.
+Three layers up to 64 streams, two beyond, where c1 drops its last layer and c5 its first.
+
+The one column with another layer count, at 94 and 126 streams ("94_deep", "126_deep"; in no batch): six layers, the recursion of
+the wide kernels across five interfaces on ill-conditioned layers --
+  deep  Rayleigh 0.95 (0.3 thick) / cloud C1 with delta-M, omega = 1 - 1e-6 (0.8) / isotropic 0.5 (1e-3: a thin layer) / Rayleigh,
+        omega = 1 - 1e-6 (0.9) / cloud C1 with delta-M, 0.9 (9.0: the Stamnes-Conklin scaling at work) / non-scattering (2.0);
+        beam, Lambertian 0.3, no thermal source.
 g, g1, g2 and b shrink with the stream count so that every truncation  sum_{l < NQuad} (2l + 1) chi*_l P_l  (delta-M-scaled where
 f > 0) is a phase function: non-negative over 4001 angles (tests/test_phase_truth_cpu.py asserts it).
 
@@ -30,8 +40,10 @@ HP_DIR = os.path.join(HERE, "golden", "hp")
 
 FULL = (6, 14, 30, 62, 126)  # all six columns
 MIX_ONLY = (8, 16, 32, 64, 128)  # c5 only
+PADDED = (10, 18, 34, 66, 94, 96, 98)  # all six columns: the most-padded ends of the widths, and the 48-lane class (66 ... 96)
+DEEP = (94, 126)  # the six-layer column "deep"
 COLUMNS = ("c0", "c1", "c2", "c3", "c4", "c5")
-NEAR_CONSERVATIVE = ("c0", "c1", "c5")
+NEAR_CONSERVATIVE = ("c0", "c1", "c5", "deep")
 NFOURIER = 3
 PHI = np.array([0.0, 0.7, 3.0])
 NEGATIVE = "8_neg"
@@ -40,6 +52,9 @@ MU0, I0, PHI0 = 0.6, 2.0, 0.5
 #  NQuad: (g of c2, (b, g1, g2) of c3): the largest round figures whose NQuad-term truncation stays non-negative
 HG_PARAMETERS = {6: (-0.5, (0.8, 0.6, -0.4)), 14: (-0.65, (0.8, 0.8, -0.5)), 30: (-0.75, (0.8, 0.9, -0.7)),
                  62: (-0.85, (0.8, 0.92, -0.8)), 126: (-0.9, (0.8, 0.95, -0.85))}
+# the PADDED stream counts take the entry of the next smaller count of FULL
+HG_PARAMETERS.update({10: HG_PARAMETERS[6], 18: HG_PARAMETERS[14], 34: HG_PARAMETERS[30],
+                      66: HG_PARAMETERS[62], 94: HG_PARAMETERS[62], 96: HG_PARAMETERS[62], 98: HG_PARAMETERS[62]})
 # Cloud C1 itself admits no such choice, and at 6 streams its delta-M-scaled truncation dips to -0.0078: there, and only there, the
 # cloud layer of c5 is 95 % cloud C1 + 5 % Rayleigh (a cloud with molecular scattering between the droplets; minimum +0.074), still
 # a tabulated Mie sequence and no geometric one.  Every other stream count takes the C1 moments as they are (minima 0.0076 ... 0.030).
@@ -92,7 +107,8 @@ def _surface_mode(m):
 
 
 def keys():
-    return [f"{q}_{c}" for q in FULL for c in COLUMNS] + [f"{q}_c5" for q in MIX_ONLY]
+    return ([f"{q}_{c}" for q in FULL for c in COLUMNS] + [f"{q}_c5" for q in MIX_ONLY]
+            + [f"{q}_{c}" for q in PADDED for c in COLUMNS] + [f"{q}_deep" for q in DEEP])
 
 
 def case(key):
@@ -107,7 +123,12 @@ def case(key):
     N, n, L = NQuad // 2, NQuad + 1, layer_count(NQuad)
     last = slice(None, L)  # two layers: the first two ...
     kw = dict(tau_arr=np.array([0.3, 1.1, 2.0])[:L], NQuad=NQuad, NFourier=NFOURIER, mu0=MU0, I0=I0, phi0=PHI0)
-    if col == "c0":
+    if col == "deep":
+        c1 = cloud_c1(n)
+        kw.update(tau_arr=np.cumsum([0.3, 0.8, 1e-3, 0.9, 9.0, 2.0]), omega_arr=np.array([0.95, 1 - 1e-6, 0.5, 1 - 1e-6, 0.9, 0.0]),
+                  Leg_coeffs_all=np.stack([rayleigh(n), c1, isotropic(n), rayleigh(n), c1, isotropic(n)]),
+                  f_arr=np.array([0.0, c1[NQuad], 0.0, 0.0, c1[NQuad], 0.0]), BDRF_Fourier_modes=[0.3])
+    elif col == "c0":
         kw.update(omega_arr=np.array([1 - 1e-6, 0.7, 1 - 1e-6])[[0, 2] if L == 2 else [0, 1, 2]],
                   Leg_coeffs_all=np.tile(rayleigh(n), (L, 1)), BDRF_Fourier_modes=[0.3])
     elif col == "c1":

@@ -22,14 +22,18 @@ three parties.  Nakajima-Tanaka corrections are post-processing and are left out
 Fixtures: tests/golden/hp/<family>_<seed>.npz = the evaluation points, u [Q, ntau, nphi], u0, flux_up of the truth and,
 for the record, the oracle's distance to it.  Families: random32 / random64 / random (the seeded generators of
 tests/test_gpu_random_parity.py), golden (a reference-captured case of tests/golden/ref by name) and phase (a column of
-tests/phase_cases.py, "<NQuad>_<column>": phase functions beyond Henyey-Greenstein; these fixtures also carry both parts of flux_down).
+tests/phase_cases.py, "<NQuad>_<column>": phase functions beyond Henyey-Greenstein, six columns c0 ... c5 per stream count and the
+six-layer column "deep" at 94 and 126 streams; these fixtures also carry both parts of flux_down).
 
 Usage (build container; minutes per case on 6 processes):
     python3 tools/hp_truth_case.py random32 9 25          # family, seeds ...
     python3 tools/hp_truth_case.py random64 11
     python3 tools/hp_truth_case.py golden 8ARTS_A
     python3 tools/hp_truth_case.py synth cfg4_9 cfg5_0     # a column of a synthetic BASELINE config (cfg5: ~1.5 h)
-    python3 tools/hp_truth_case.py phase 30_c3 62_c5      # columns of tests/phase_cases.py; "phase all": every one (~7 min on 8 processes)
+    python3 tools/hp_truth_case.py phase 30_c3 94_deep    # columns of tests/phase_cases.py; "phase all": every one of the 80 (~15 min
+                                                          # with HP_WORKERS=8: the 36 up to 128 streams of the first set ~7 min, the 44
+                                                          # of the padded stream counts and the deep column ~7 min, 126_deep alone ~4)
+    python3 tools/hp_truth_case.py phase all --skip-existing   # only the cases whose fixture is missing
     python3 tools/hp_truth_case.py --near-conservative    # every random32 / random64 seed with an omega > 1 - 1e-5 layer
 """
 import multiprocessing
