@@ -181,6 +181,43 @@ int rtd_plan_set_columns_thermal(rtd_plan* plan, const double* tau_arr, const do
                                  const double* phi0, const double* b_pos, const double* b_neg, const double* bdrf_q,
                                  const double* bdrf_q0, const rtd_thermal* th);
 
+/* k-distribution bands: the optical properties of P profiles x G spectral points mixed on the device.  Within a band (the
+ * g-points of a correlated-k band, the wavelengths of an instrument channel) every column of a profile shares its scatterers,
+ * its geometry and its surface; only the gas absorption per layer and the solar weight change from point to point.  The caller
+ * states the band as it has it -- G + 2 S doubles per profile and layer instead of the 3 + nleg per column and layer of
+ * rtd_plan_set_columns_raw -- and the device forms tau_arr, omega_arr, f_arr and the moments of every column c = p G + g:
+ *   sca   = sum_s omega_spec[p][l][s] dtau_spec[p][l][s]
+ *   dtau  = sum_s dtau_spec[p][l][s] + dtau_abs[p][g][l]
+ *   tau_arr[c][l] = dtau[c][0] + ... + dtau[c][l],   omega_arr[c][l] = sca / dtau
+ *   leg_all[c][l][k] = sum_s omega_spec dtau_spec leg_spec[s][k] / sca  (k >= 1; 1 for k = 0),   k < nleg
+ *   f_arr[c][l] = the same expression at k = nleg when delta_m is set (needs nleg_all > nleg), else 0
+ * with s and l ascending and one thread per output element: the bits do not depend on the launch geometry.  A layer without a
+ * scatterer (sca = 0) gets the moments (1, 0, ...) and f = 0.  The mixed leg_all has nleg moments per layer ([C][L][nleg]): those
+ * the solver uses. */
+typedef struct {
+  int32_t nprofiles, ngpoints, nspecies, nleg_all, delta_m;
+  const double *dtau_abs;   /* [P][G][L] absorption optical thickness of each layer at each spectral point (>= 0) */
+  const double *dtau_spec;  /* [P][L][S] extinction optical thickness of each species in each layer (>= 0)        */
+  const double *omega_spec; /* [P][L][S] single-scattering albedo of each species (0 ... 1)                       */
+  const double *leg_spec;   /* [S][nleg_all] Legendre coefficients of each species' phase function, [s][0] = 1    */
+} rtd_band;
+
+/* The plan-free form, like rtd_planck_band: host arrays in, the four mixed arrays out (tau_arr, omega_arr, f_arr [P G][L],
+ * leg_all [P G][L][nleg]), synchronous.  RTD_ERR_ARG for a null pointer, P, G, S or nlayers < 1, nleg < 1, or
+ * nleg_all < nleg + (delta_m ? 1 : 0). */
+int rtd_band_mix(int32_t device, int32_t nlayers, int32_t nleg, const rtd_band* band, double* tau_arr, double* omega_arr,
+                 double* f_arr, double* leg_all);
+
+/* rtd_plan_set_columns_raw with tau_arr, omega_arr, f_arr and leg_all formed on the device from `band`; the plan must have
+ * ncols = P G.  mu0, I0, phi0 [C] and the boundary and BDRF arrays as there (per column).  th may be NULL; given, the isotropic
+ * source is formed as by rtd_plan_set_columns_thermal (plan with nscoeffs = 2, else no isotropic source: nscoeffs = 0) -- its
+ * slopes use the mixed tau.  tau_out [C][L] (may be NULL) receives the mixed tau_arr as the device formed it: the optical depths
+ * of the levels, which the caller needs to name an evaluation point.  Not combined with rtd_plan_set_mode_shard or a
+ * communicator (RTD_ERR_STATE). */
+int rtd_plan_set_columns_band(rtd_plan* plan, const rtd_band* band, const double* mu0, const double* I0, const double* phi0,
+                              const double* b_pos, const double* b_neg, const double* bdrf_q, const double* bdrf_q0,
+                              const rtd_thermal* th, double* tau_out);
+
 /* BDRF Fourier modes formed on the device.  The reference takes the surface as callables
  * BDRF_Fourier_modes[m](mu, -mu') evaluated on the quadrature grid (_solve_for_coeffs.py:121-134); for a reflectance
  * rho(mu, mu', dphi) its tests integrate every mode on the host (pydisotest/6_test.py:194-201).  Here the caller passes
@@ -258,6 +295,26 @@ int rtd_plan_fetch(rtd_plan* plan, double* u, double* u0, double* flux_up, doubl
  * staging on a copy stream -> the caller's arrays) while window w+1 is being solved.  Synchronous; any pointer may be NULL. */
 int rtd_plan_run_fetch(rtd_plan* plan, double* u, double* u0, double* flux_up, double* flux_down_diffuse,
                        double* flux_down_direct);
+/* Spectral integration of the results on the device: with weights set, consecutive groups of G columns are the spectral points
+ * of one profile (column c = p G + g, P = ncols / G), and
+ *   out[p][k][e] = sum_g w[k][g] X[p G + g][e]
+ * for each of K >= 1 weight sets (k-distribution weights, several channels' response functions, photolysis cross sections) and
+ * every element e of a column's result X.  The t-th evaluation point of each of a profile's columns must be the same physical
+ * level: that is the caller's contract.  The sum is accumulated in double-double (exact products, g ascending) and rounded once:
+ * it is the correctly rounded sum to within 2^-90 sum_g |w x|, whatever the window size.  w [K][G]; ncols % G == 0 and K >= 1,
+ * else RTD_ERR_ARG; G <= 0 switches the stage off.  Not combined with rtd_plan_set_mode_shard or a communicator (RTD_ERR_STATE:
+ * multi-GPU band runs shard by profile and need no collective over g). */
+int rtd_plan_set_band_weights(rtd_plan* plan, int32_t ngpoints, int32_t nsets, const double* w);
+/* After rtd_plan_run: reduces the plan's result buffers on the plan's stream and copies out u [P][K][NQuad][ntau][nphi],
+ * u0 [P][K][NQuad][ntau] and the fluxes [P][K][ntau]; a NULL output is neither reduced nor copied.  Status as rtd_plan_fetch: when
+ * any of a profile's G columns has failed numerically (mode 0 for u0 and the fluxes, any mode for u) that profile's outputs are NaN,
+ * every other profile keeps its result, and the call returns RTD_ERR_NUMERIC.  rtd_plan_fetch still returns the unreduced fields. */
+int rtd_plan_fetch_band(rtd_plan* plan, double* u, double* u0, double* flux_up, double* flux_down_diffuse,
+                        double* flux_down_direct);
+/* rtd_plan_evaluate (solved or retained plan, the same flag word, the same tau-range error; tau [C][ntau]) without copying the
+ * unreduced fields out: evaluates into the device buffers, reduces, returns the reduced arrays of rtd_plan_fetch_band. */
+int rtd_plan_evaluate_band(rtd_plan* plan, int32_t ntau, const double* tau, int32_t nphi, const double* phi, int32_t flags,
+                           double* u, double* u0, double* flux_up, double* flux_down_diffuse, double* flux_down_direct);
 /* device pointers of the result buffers of rtd_plan_run (for a device-side collective) */
 int rtd_plan_result_dev_ptrs(rtd_plan* plan, void** u_dev, int64_t* u_bytes, void** flux_dev, int64_t* flux_bytes);
 

@@ -319,6 +319,12 @@ struct rtd_plan {
   int ev_ntau = 0, ev_nphi = 0;
   double *ev_tau = nullptr, *ev_phi = nullptr, *ev_u = nullptr, *ev_u0 = nullptr, *ev_fl = nullptr;
   int64_t cap_tau = 0, cap_phi = 0, cap_u = 0, cap_u0 = 0, cap_fl = 0;
+  // k-distribution bands (rtd_plan_set_columns_band, rtd_plan_set_band_weights): the columns are P profiles x band_G spectral points;
+  // band_w [K][G] on the device, the reduced results [P][K][...] grown on demand like the evaluation buffers
+  bool band_cols = false;
+  int band_G = 0, band_K = 0;
+  double *band_w = nullptr, *rb_u = nullptr, *rb_u0 = nullptr, *rb_fl = nullptr;
+  int64_t cap_band_w = 0, cap_rb_u = 0, cap_rb_u0 = 0, cap_rb_fl = 0;
   // export buffers
   double* ex_buf = nullptr;
   // Nakajima-Tanaka corrections (optional)
@@ -701,7 +707,7 @@ extern "C" {
 
 int rtd_comm_destroy(rtd_plan* p);
 
-int rtd_version(void) { return 212; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6)
+int rtd_version(void) { return 213; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band
 
 const char* rtd_last_error(void) { return g_err.c_str(); }
 
@@ -1161,6 +1167,7 @@ int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* 
     HIP_TRY(hipStreamSynchronize(s));  // the caller's arrays and the host staging vectors must outlive their copies
   }
   p->h_tau.assign(tau, tau + C * L);
+  p->band_cols = false;
   p->ev_iface = false;  // stored evaluation points, if any, are no longer known to be this batch's interfaces
   p->have_cols = true;
   p->fork_needed = true;
@@ -1231,6 +1238,136 @@ __global__ void rtd_thermal_sources_kernel(RtdDev d, RtdThermalDev t) {
   }
 }
 
+// k-distribution bands (include/rtd.h: rtd_band): the optical properties of the columns c = p G + g mixed from the band's small
+// arrays, and the spectral integral of the results.  Streaming kernels, one thread per output element with the fastest thread
+// index along the contiguous axis; no LDS, no barrier, no cross-lane operation (the stand-in runtime of tests/cpu runs them
+// thread by thread).  Loop orders are fixed (s ascending, l ascending, g ascending): no result depends on the launch geometry.
+struct RtdBandDev {
+  long P;
+  int G, S, L, nleg, nleg_all, delta_m;
+  const double *abs, *dspec, *ospec, *lspec;  // the caller's arrays (staged): [P][G][L], [P][L][S], [P][L][S], [S][nleg_all]
+  double *tau, *omega, *f, *leg;              // [C][L] x 3, [C][L][nleg]: the raw arrays the preparation kernel reads
+};
+
+// one thread per (c, l), l fastest: omega, f, and the layer's optical thickness in tau's place
+__global__ void rtd_band_layers_kernel(RtdBandDev b) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= b.P * b.G * b.L) return;
+  const long c = idx / b.L, p = c / b.G;
+  const int l = (int)(idx % b.L), g = (int)(c % b.G);
+  const double* dt = b.dspec + (p * b.L + l) * b.S;
+  const double* om = b.ospec + (p * b.L + l) * b.S;
+  double sca = 0.0, ext = 0.0, fs = 0.0;
+  for (int s = 0; s < b.S; ++s) {
+    const double t = om[s] * dt[s];
+    sca += t;
+    ext += dt[s];
+    if (b.delta_m) fs += t * b.lspec[(long)s * b.nleg_all + b.nleg];
+  }
+  const double dtau = ext + b.abs[(p * b.G + g) * b.L + l];
+  b.tau[idx] = dtau;
+  b.omega[idx] = sca / dtau;
+  b.f[idx] = (b.delta_m && sca != 0.0) ? fs / sca : 0.0;
+}
+
+// one thread per column: the running sum of the layers' thicknesses, in place (L is tens)
+__global__ void rtd_band_tau_kernel(RtdBandDev b) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= b.P * b.G) return;
+  double* t = b.tau + c * b.L;
+  double run = 0.0;
+  for (int l = 0; l < b.L; ++l) {
+    run += t[l];
+    t[l] = run;
+  }
+}
+
+// one thread per (c, l, k), k fastest: the moments of the mixture (they do not depend on g: the absorber does not scatter)
+__global__ void rtd_band_moments_kernel(RtdBandDev b) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= b.P * b.G * b.L * b.nleg) return;
+  const int k = (int)(idx % b.nleg);
+  const long cl = idx / b.nleg, c = cl / b.L, p = c / b.G;
+  const int l = (int)(cl % b.L);
+  const double* dt = b.dspec + (p * b.L + l) * b.S;
+  const double* om = b.ospec + (p * b.L + l) * b.S;
+  double sca = 0.0, num = 0.0;
+  for (int s = 0; s < b.S; ++s) {
+    const double t = om[s] * dt[s];
+    sca += t;
+    num += t * b.lspec[(long)s * b.nleg_all + k];
+  }
+  b.leg[idx] = k == 0 ? 1.0 : sca != 0.0 ? num / sca : 0.0;
+}
+
+void band_mix_launch(const RtdBandDev& b, hipStream_t s) {
+  const long C = b.P * b.G, n_cl = C * b.L, n_leg = n_cl * b.nleg;
+  hipLaunchKernelGGL(rtd_band_layers_kernel, dim3((unsigned)((n_cl + 255) / 256)), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(rtd_band_tau_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(rtd_band_moments_kernel, dim3((unsigned)((n_leg + 255) / 256)), dim3(256), 0, s, b);
+}
+
+// argument check shared by rtd_band_mix and rtd_plan_set_columns_band; returns nullptr when the band is fine
+const char* band_bad(const rtd_band* b, int64_t nleg) {
+  if (!b || !b->dtau_abs || !b->dtau_spec || !b->omega_spec || !b->leg_spec) return "band: null argument";
+  if (b->nprofiles < 1 || b->ngpoints < 1) return "band: need nprofiles >= 1 and ngpoints >= 1";
+  if (b->nspecies < 1) return "band: need at least one scatterer species";
+  if ((int64_t)b->nprofiles * b->ngpoints > INT32_MAX) return "band: nprofiles x ngpoints exceeds the column count of a plan";
+  if (b->nleg_all < nleg + (b->delta_m ? 1 : 0)) return "band: nleg_all must be >= nleg (+ 1 with delta_m)";
+  return nullptr;
+}
+
+// out[p][k][e] = sum_g w[k][g] X[p G + g][e]: one thread per (p, e), e fastest, so that the reads of X are contiguous across the
+// wavefront; K accumulators in double-double (exact products, rtd_dd.h) held in registers in chunks of at most 4 -- X is read
+// again for further chunks; the kernel is bound by that read, the arithmetic hides behind it.  mask: the bits of col_status that
+// spoil this output (0xFF: mode 0 alone for u0 and the fluxes; 0xFFFF for u) -- a profile with such a column is NaN.
+//
+// The rounded product passes through rtd_band_opaque on its way from rtd_two_prod to rtd_dd_add.  The device compiler contracts
+// floating-point expressions across inlined functions: a + fl(w v) would become fma(w, v, a), the error term of the two-sum would
+// then already hold the product's rounding error, and the low half of rtd_two_prod would add it a second time -- a sum no better
+// than a float64 one.  An empty asm statement that names the register keeps the multiplication and the addition apart.
+__device__ __host__ inline double rtd_band_opaque(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(x));
+#endif
+  return x;
+}
+
+extern "C++" template <int NK>  // (this part of the file has C linkage for the entry points)
+__device__ __host__ inline void rtd_band_reduce_chunk(const double* x, const double* w, int G, long E, bool bad, double* out) {
+  rtd_dd acc[NK];
+  for (int j = 0; j < NK; ++j) acc[j] = {0.0, 0.0};
+  for (int g = 0; g < G; ++g) {
+    const double v = x[(long)g * E];
+    for (int j = 0; j < NK; ++j) {
+      rtd_dd t = rtd_two_prod(w[(long)j * G + g], v);
+      t.hi = rtd_band_opaque(t.hi);
+      acc[j] = rtd_dd_add(acc[j], t);
+    }
+  }
+  for (int j = 0; j < NK; ++j) out[(long)j * E] = bad ? __builtin_nan("") : acc[j].hi + acc[j].lo;
+}
+
+__global__ void rtd_band_reduce_kernel(const double* X, const double* w, const int* col_status, int mask, long P, int G, int K,
+                                       long E, double* out) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= P * E) return;
+  const long p = idx / E, e = idx % E;
+  bool bad = false;
+  for (int g = 0; g < G; ++g) bad = bad || (col_status[p * G + g] & mask) != 0;
+  const double* x = X + p * G * E + e;
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    const double* wk = w + (long)k0 * G;
+    double* o = out + (p * K + k0) * E + e;
+    switch (K - k0) {
+      case 1: rtd_band_reduce_chunk<1>(x, wk, G, E, bad, o); break;
+      case 2: rtd_band_reduce_chunk<2>(x, wk, G, E, bad, o); break;
+      case 3: rtd_band_reduce_chunk<3>(x, wk, G, E, bad, o); break;
+      default: rtd_band_reduce_chunk<4>(x, wk, G, E, bad, o); break;
+    }
+  }
+}
+
 }  // namespace
 
 int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wvnmlo, const double* wvnmhi, double* out) {
@@ -1257,14 +1394,25 @@ int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wv
   return 0;
 }
 
-// rtd_plan_set_columns_raw (th == nullptr: exactly its copies and launches) and rtd_plan_set_columns_thermal (s_poly == nullptr,
-// the source polynomials and the boundary emissions are formed in the staging block before the preparation kernel reads it)
+// rtd_plan_set_columns_raw (th == nullptr: exactly its copies and launches), rtd_plan_set_columns_thermal (s_poly == nullptr,
+// the source polynomials and the boundary emissions are formed in the staging block before the preparation kernel reads it) and
+// rtd_plan_set_columns_band (band != nullptr: tau_arr, omega_arr, f_arr and leg_all are not uploaded but mixed on the device into
+// the same carves of the staging block, nleg moments per layer, ahead of the thermal kernels; the mixed tau comes back into h_tau)
 static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double* omega_arr, const double* leg_all,
                                 int32_t nleg_all, const double* f_arr, const double* mu0, const double* I0,
                                 const double* phi0, const double* b_pos, const double* b_neg, const double* s_poly,
-                                const double* bdrf_q, const double* bdrf_q0, const rtd_thermal* th) {
-  if (!p || !tau_arr || !omega_arr || !leg_all || !f_arr || !mu0 || !I0 || !phi0) return fail(RTD_ERR_ARG, "null argument");
+                                const double* bdrf_q, const double* bdrf_q0, const rtd_thermal* th, const rtd_band* band = nullptr,
+                                double* tau_out = nullptr) {
+  if (!p || !mu0 || !I0 || !phi0) return fail(RTD_ERR_ARG, "null argument");
+  if (!band && (!tau_arr || !omega_arr || !leg_all || !f_arr)) return fail(RTD_ERR_ARG, "null argument");
   const RtdDev& d = p->d;
+  if (band) {
+    if (const char* bad = band_bad(band, d.P)) return fail(RTD_ERR_ARG, bad);
+    if ((int64_t)band->nprofiles * band->ngpoints != d.C) return fail(RTD_ERR_ARG, "band: the plan must have ncols = nprofiles x ngpoints");
+    if (p->comm || d.m0 != 0 || d.mstep != 1 || d.mtot != d.M)
+      return fail(RTD_ERR_STATE, "band inputs are not combined with a mode shard or a communicator");
+    nleg_all = d.P;  // the staging block holds the moments the solver uses
+  }
   if (nleg_all < d.P) return fail(RTD_ERR_ARG, "nleg_all must be >= nleg");
   if (th) {
     if (d.Ns != 2) return fail(RTD_ERR_ARG, "thermal sources need a plan with nscoeffs = 2");
@@ -1287,7 +1435,9 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   const int64_t n_th = !th ? 0
                            : C * (L + 1) + 2 * C + (th->btemp ? C : 0) + (th->ttemp ? C : 0) + (th->temis ? C : 0) +
                                  (th->emissivity ? C * N : 0) + C * (L + 3) + (th_bpos && !b_pos ? n_b : 0) + (th_bneg && !b_neg ? n_b : 0);
-  const int64_t total = 3 * n_cl + n_leg + 3 * C + (b_pos ? n_b : 0) + (b_neg ? n_b : 0) + n_sp + n_th;
+  const int64_t bP = band ? band->nprofiles : 0, bG = band ? band->ngpoints : 0, bS = band ? band->nspecies : 0;
+  const int64_t n_abs = bP * bG * L, n_spec = bP * L * bS, n_lspec = band ? bS * band->nleg_all : 0, n_band = n_abs + 2 * n_spec + n_lspec;
+  const int64_t total = 3 * n_cl + n_leg + 3 * C + (b_pos ? n_b : 0) + (b_neg ? n_b : 0) + n_sp + n_th + n_band;
   // staging block from the process-wide pool (a raw hipMalloc / hipFree pair synchronises the whole device per call)
   void* raw_v = nullptr;
   size_t raw_got = 0;
@@ -1302,7 +1452,14 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     if (e == hipSuccess && n > 0) e = hipMemcpyAsync(q, src, (size_t)n * 8, hipMemcpyHostToDevice, s);
     q += n;
   };
-  up(r.tau, tau_arr, n_cl); up(r.omega, omega_arr, n_cl); up(r.f, f_arr, n_cl); up(r.leg, leg_all, n_leg);
+  RtdBandDev bd{};
+  if (band) {  // the four carves are written by the mix kernels
+    bd.tau = q; bd.omega = q + n_cl; bd.f = q + 2 * n_cl; bd.leg = q + 3 * n_cl;
+    r.tau = bd.tau; r.omega = bd.omega; r.f = bd.f; r.leg = bd.leg;
+    q += 3 * n_cl + n_leg;
+  } else {
+    up(r.tau, tau_arr, n_cl); up(r.omega, omega_arr, n_cl); up(r.f, f_arr, n_cl); up(r.leg, leg_all, n_leg);
+  }
   up(r.mu0, mu0, C); up(r.I0, I0, C); up(r.phi0, phi0, C);
   if (b_pos) up(r.bpos, b_pos, n_b);
   if (b_neg) up(r.bneg, b_neg, n_b);
@@ -1329,6 +1486,15 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   } else if (Ns > 0) {
     up(r.spoly, s_poly, n_sp);
   }
+  if (band) {
+    bd.P = bP; bd.G = (int)bG; bd.S = (int)bS; bd.L = (int)L; bd.nleg = d.P; bd.nleg_all = band->nleg_all; bd.delta_m = band->delta_m ? 1 : 0;
+    up(bd.abs, band->dtau_abs, n_abs); up(bd.dspec, band->dtau_spec, n_spec); up(bd.ospec, band->omega_spec, n_spec);
+    up(bd.lspec, band->leg_spec, n_lspec);
+    if (e == hipSuccess) {  // ahead of the thermal kernels, whose source slopes read the mixed tau
+      band_mix_launch(bd, s);
+      e = hipGetLastError();
+    }
+  }
   std::vector<double> qh, q0h;
   if (e == hipSuccess && NB > 0) {  // BDRF tables: padded from N to NP on the host (small)
     qh.assign((size_t)(C * NB * NP * NP), 0.0);
@@ -1351,11 +1517,20 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     rtd_launch_prepare(d, r, s);
     e = hipGetLastError();
   }
+  if (band) {  // the host never recomputes tau: the interface detection of rtd_plan_set_eval_points compares the device's bits
+    p->h_tau.resize((size_t)n_cl);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->h_tau.data(), r.tau, (size_t)n_cl * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && tau_out) e = hipMemcpyAsync(tau_out, r.tau, (size_t)n_cl * 8, hipMemcpyDeviceToHost, s);
+  }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   else (void)hipStreamSynchronize(s);  // nothing may still read the block when it goes back to the pool
   pooled_free(raw, raw_got, p->device);
-  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("set_columns_raw: ") + hipGetErrorString(e));
-  p->h_tau.assign(tau_arr, tau_arr + C * L);
+  if (e != hipSuccess) {
+    if (band) p->h_tau.clear();
+    return fail(RTD_ERR_HIP, std::string("set_columns_raw: ") + hipGetErrorString(e));
+  }
+  if (!band) p->h_tau.assign(tau_arr, tau_arr + C * L);
+  p->band_cols = band != nullptr;
   p->ev_iface = false;
   p->have_cols = true;
   p->fork_needed = true;
@@ -1379,6 +1554,49 @@ int rtd_plan_set_columns_thermal(rtd_plan* p, const double* tau_arr, const doubl
                                  const double* bdrf_q0, const rtd_thermal* th) {
   if (!th) return fail(RTD_ERR_ARG, "thermal: null description");
   return set_columns_raw_impl(p, tau_arr, omega_arr, leg_all, nleg_all, f_arr, mu0, I0, phi0, b_pos, b_neg, nullptr, bdrf_q, bdrf_q0, th);
+}
+
+int rtd_plan_set_columns_band(rtd_plan* p, const rtd_band* band, const double* mu0, const double* I0, const double* phi0,
+                              const double* b_pos, const double* b_neg, const double* bdrf_q, const double* bdrf_q0,
+                              const rtd_thermal* th, double* tau_out) {
+  if (!p || !band) return fail(RTD_ERR_ARG, "band: null argument");
+  if (!th && p->d.Ns > 0) return fail(RTD_ERR_ARG, "band: a plan with nscoeffs > 0 needs the thermal description");
+  return set_columns_raw_impl(p, nullptr, nullptr, nullptr, 0, nullptr, mu0, I0, phi0, b_pos, b_neg, nullptr, bdrf_q, bdrf_q0, th, band,
+                              tau_out);
+}
+
+int rtd_band_mix(int32_t device, int32_t nlayers, int32_t nleg, const rtd_band* band, double* tau_arr, double* omega_arr,
+                 double* f_arr, double* leg_all) {
+  if (nlayers < 1 || nleg < 1 || !tau_arr || !omega_arr || !f_arr || !leg_all) return fail(RTD_ERR_ARG, "band_mix: null argument or size < 1");
+  if (const char* bad = band_bad(band, nleg)) return fail(RTD_ERR_ARG, bad);
+  HIP_TRY(hipSetDevice(device));
+  const int64_t P = band->nprofiles, G = band->ngpoints, S = band->nspecies, L = nlayers, C = P * G;
+  const int64_t n_cl = C * L, n_leg = n_cl * nleg, n_abs = P * G * L, n_spec = P * L * S, n_lspec = S * band->nleg_all;
+  void* buf_v = nullptr;
+  size_t got = 0;
+  HIP_TRY(pooled_malloc(&buf_v, (size_t)(3 * n_cl + n_leg + n_abs + 2 * n_spec + n_lspec) * 8, device, &got));
+  double* buf = (double*)buf_v;
+  RtdBandDev b{};
+  b.P = P; b.G = (int)G; b.S = (int)S; b.L = (int)L; b.nleg = nleg; b.nleg_all = band->nleg_all; b.delta_m = band->delta_m ? 1 : 0;
+  b.tau = buf; b.omega = buf + n_cl; b.f = buf + 2 * n_cl; b.leg = buf + 3 * n_cl;
+  double* in = buf + 3 * n_cl + n_leg;
+  b.abs = in; b.dspec = in + n_abs; b.ospec = in + n_abs + n_spec; b.lspec = in + n_abs + 2 * n_spec;
+  hipError_t e = hipMemcpy(in, band->dtau_abs, (size_t)n_abs * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(in + n_abs, band->dtau_spec, (size_t)n_spec * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(in + n_abs + n_spec, band->omega_spec, (size_t)n_spec * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(in + n_abs + 2 * n_spec, band->leg_spec, (size_t)n_lspec * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    band_mix_launch(b, (hipStream_t)0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(tau_arr, b.tau, (size_t)n_cl * 8, hipMemcpyDeviceToHost);  // (waits for the kernels)
+  else (void)hipStreamSynchronize((hipStream_t)0);
+  if (e == hipSuccess) e = hipMemcpy(omega_arr, b.omega, (size_t)n_cl * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(f_arr, b.f, (size_t)n_cl * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(leg_all, b.leg, (size_t)n_leg * 8, hipMemcpyDeviceToHost);
+  pooled_free(buf, got, device);
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("band_mix: ") + hipGetErrorString(e));
+  return 0;
 }
 
 int rtd_plan_set_bdrf_samples(rtd_plan* p, int32_t nphi, const double* rho_qq, const double* rho_q0) {
@@ -1415,6 +1633,8 @@ int rtd_plan_set_mode_shard(rtd_plan* p, int32_t first, int32_t stride, int32_t 
   if (first < 0 || stride < 1 || total < 1 || first + (int64_t)stride * (d.M - 1) > total - 1)
     return fail(RTD_ERR_ARG, "mode shard: need 0 <= first, stride >= 1 and first + stride (nfourier - 1) <= total - 1");
   if (total > d.P) return fail(RTD_ERR_ARG, "mode shard: total number of Fourier modes exceeds nleg");
+  if ((p->band_cols || p->band_G > 0) && (first != 0 || stride != 1 || total != d.M))
+    return fail(RTD_ERR_STATE, "mode shard: not combined with band inputs or band weights");
   d.m0 = first;
   d.mstep = stride;
   d.mtot = total;
@@ -1612,16 +1832,15 @@ int rtd_plan_result_dev_ptrs(rtd_plan* p, void** u_dev, int64_t* u_bytes, void**
   return 0;
 }
 
-int rtd_plan_evaluate(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi, const double* phi,
-                      int32_t antiderivative, double* u, double* u0, double* flux_up, double* fdn, double* fdir,
-                      double* ulast) {
-  if (!p) return fail(RTD_ERR_ARG, "null plan");
+// the evaluation of rtd_plan_evaluate / rtd_plan_evaluate_band into the plan's result buffers, queued on the plan's stream
+static int evaluate_queued(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi, const double* phi, int32_t antiderivative,
+                           bool want_u) {
   if (!p->solved) return fail(RTD_ERR_STATE, "evaluate before solve");
   if ((antiderivative & 1) && (antiderivative & 4)) return fail(RTD_ERR_ARG, "antiderivative (bit 0) and derivative (bit 2) exclude each other");
   int rc = rtd_plan_set_eval_points(p, ntau, tau, nphi, phi);
   if (rc) return rc;
   const bool skip_nt = (antiderivative & 2) != 0;
-  RtdEval e = make_eval(p, (antiderivative & 1) ? -1 : (antiderivative & 4) ? 1 : 0, u != nullptr);
+  RtdEval e = make_eval(p, (antiderivative & 1) ? -1 : (antiderivative & 4) ? 1 : 0, want_u);
   // one window, or a retained plan (rtd_plan_create_retained): what the evaluators need of the solve is resident for every
   // column, only the evaluation kernels run.  Several windows without retention: they are solved again, window by window,
   // with the evaluation behind each (the throughput form rtd_plan_run is the intended entry point for such batches).
@@ -1629,6 +1848,15 @@ int rtd_plan_evaluate(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi
   rc = launch_windows(p, solve_again, &e, p->have_nt && !skip_nt, [](int, int64_t, int) { return 0; }, false);
   if (rc) return rc;
   if (p->pipelined && !solve_again) p->fork_needed = true;  // the next solve's eigen stream must not overwrite what this pass still reads
+  return 0;
+}
+
+int rtd_plan_evaluate(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi, const double* phi,
+                      int32_t antiderivative, double* u, double* u0, double* flux_up, double* fdn, double* fdir,
+                      double* ulast) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  int rc = evaluate_queued(p, ntau, tau, nphi, phi, antiderivative, u != nullptr);
+  if (rc) return rc;
   if (ulast) {  // queued before the fetch, whose status check drains the stream: a numerical failure of SOME columns must not
     //             leave the healthy columns' ulast unwritten (numeric_errors = "nan" keeps them)
     const int64_t C = p->d.C, Qr = 2 * p->d.N;
@@ -1636,6 +1864,69 @@ int rtd_plan_evaluate(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi
     if (he != hipSuccess) return drained(p, fail(RTD_ERR_HIP, std::string("hipMemcpyAsync(ulast): ") + hipGetErrorString(he)));
   }
   return drained(p, rtd_plan_fetch(p, u, u0, flux_up, fdn, fdir));  // (also behind fetch's own early returns: the ulast copy is pending)
+}
+
+int rtd_plan_set_band_weights(rtd_plan* p, int32_t G, int32_t K, const double* w) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (G <= 0) {  // switch the reduction off
+    p->band_G = p->band_K = 0;
+    return 0;
+  }
+  if (K < 1 || !w || p->d.C % G != 0) return fail(RTD_ERR_ARG, "band weights: need nsets >= 1, weights and ncols % ngpoints == 0");
+  if (p->comm || p->d.m0 != 0 || p->d.mstep != 1 || p->d.mtot != p->d.M)
+    return fail(RTD_ERR_STATE, "band weights are not combined with a mode shard or a communicator");
+  HIP_TRY(hipSetDevice(p->device));
+  int rc = grow(p, &p->band_w, &p->cap_band_w, (int64_t)K * G);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(p->band_w, w, (size_t)K * G * 8, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));  // the caller's array must outlive its copy
+  p->band_G = G;
+  p->band_K = K;
+  return 0;
+}
+
+// reduce the result buffers over the spectral points on the plan's stream, copy the reduced arrays out, check the status
+static int band_fetch_queued(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir) {
+  HIP_TRY(hipSetDevice(p->device));
+  const int64_t G = p->band_G, K = p->band_K, P = p->d.C / G, Qr = 2 * p->d.N, nt = p->ev_ntau, np = p->ev_nphi;
+  const int64_t Eu = Qr * nt * np, Eu0 = Qr * nt;
+  hipStream_t s = p->stream;
+  double* fls[3] = {flux_up, fdn, fdir};
+  int rc;
+  if (u && np > 0 && (rc = grow(p, &p->rb_u, &p->cap_rb_u, P * K * Eu))) return rc;
+  if (u0 && (rc = grow(p, &p->rb_u0, &p->cap_rb_u0, P * K * Eu0))) return rc;
+  if ((flux_up || fdn || fdir) && (rc = grow(p, &p->rb_fl, &p->cap_rb_fl, 3 * P * K * nt))) return rc;
+  (void)hipGetLastError();
+  auto reduce = [&](const double* X, int mask, int64_t E, double* out, double* host) -> hipError_t {
+    hipLaunchKernelGGL(rtd_band_reduce_kernel, dim3((unsigned)((P * E + 255) / 256)), dim3(256), 0, s, X, (const double*)p->band_w,
+                       (const int*)p->d.col_status, mask, (long)P, (int)G, (int)K, (long)E, out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host, out, (size_t)(P * K * E) * 8, hipMemcpyDeviceToHost, s);
+    return e;
+  };
+  hipError_t e = hipSuccess;
+  if (u && np > 0) e = reduce(p->ev_u, 0xFFFF, Eu, p->rb_u, u);
+  if (e == hipSuccess && u0) e = reduce(p->ev_u0, 0xFF, Eu0, p->rb_u0, u0);  // (u0 and the fluxes come from Fourier mode 0 alone)
+  for (int f = 0; f < 3; ++f)
+    if (e == hipSuccess && fls[f]) e = reduce(p->ev_fl + f * p->d.C * nt, 0xFF, nt, p->rb_fl + f * P * K * nt, fls[f]);
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("fetch_band: ") + hipGetErrorString(e));
+  return check_status(p, u != nullptr);
+}
+
+int rtd_plan_fetch_band(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede fetch_band");
+  if (p->ev_ntau < 1 || !p->solved) return fail(RTD_ERR_STATE, "nothing to fetch");
+  return drained(p, band_fetch_queued(p, u, u0, flux_up, fdn, fdir));
+}
+
+int rtd_plan_evaluate_band(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi, const double* phi, int32_t flags, double* u,
+                           double* u0, double* flux_up, double* fdn, double* fdir) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede evaluate_band");
+  int rc = evaluate_queued(p, ntau, tau, nphi, phi, flags, u != nullptr);
+  if (rc) return rc;
+  return drained(p, band_fetch_queued(p, u, u0, flux_up, fdn, fdir));
 }
 
 int rtd_plan_set_nt(rtd_plan* p, int32_t nleg_all, const double* weighted_leg_all, const double* f_arr,
@@ -1893,6 +2184,7 @@ int rtd_comm_unique_id(char id[128]) {
 
 int rtd_comm_init(rtd_plan* p, const char id[128], int32_t rank, int32_t nranks) {
   if (!p || !id || rank < 0 || rank >= nranks) return fail(RTD_ERR_ARG, "bad communicator arguments");
+  if (p->band_cols || p->band_G > 0) return fail(RTD_ERR_STATE, "communicator: not combined with band inputs or band weights");
   RcclApi* r = rccl();
   if (!r) return fail(RTD_ERR_HIP, "librccl.so could not be loaded");
   HIP_TRY(hipSetDevice(p->device));

@@ -7,7 +7,8 @@ numerics run in hand-written HIP kernels (librtd.so) reached through the C ABI o
 from .pydisort import pydisort  # noqa: F401
 from .batch import pydisort_batch, BatchSolution, solve_columns_streamed  # noqa: F401
 from . import subroutines  # noqa: F401
-from ._engine import Plan as _Plan, planck_band  # noqa: F401
+from .band import pydisort_band, BandSolution, solve_band_streamed  # noqa: F401
+from ._engine import Plan as _Plan, planck_band, band_mix  # noqa: F401
 
 import contextlib as _contextlib
 
@@ -29,5 +30,5 @@ def pooled(nbytes=-1, device=0):
         pool_set_limit(prev, device)
 
 
-__all__ = ["pydisort", "pydisort_batch", "BatchSolution", "solve_columns_streamed", "subroutines", "planck_band", "pool_bytes",
-           "pool_trim", "pool_set_limit", "pooled"]
+__all__ = ["pydisort", "pydisort_batch", "BatchSolution", "solve_columns_streamed", "pydisort_band", "BandSolution",
+           "solve_band_streamed", "band_mix", "subroutines", "planck_band", "pool_bytes", "pool_trim", "pool_set_limit", "pooled"]

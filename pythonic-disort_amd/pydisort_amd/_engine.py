@@ -31,7 +31,9 @@ class Plan:
         self._h = h
         mu, w = _f64(prep["mu"]), _f64(prep["W"])
         _lib.check(lib.rtd_plan_set_quadrature(h, _lib.dptr(mu), _lib.dptr(w)))
-        if prep.get("raw") is not None and prep.get("thermal") is not None:
+        if prep.get("band") is not None:
+            self.set_columns_band(prep["band"], prep["cols"], prep.get("thermal"))
+        elif prep.get("raw") is not None and prep.get("thermal") is not None:
             self.set_columns_thermal(prep["raw"], prep["thermal"])
         elif prep.get("raw") is not None:
             self.set_columns_raw(prep["raw"])
@@ -43,8 +45,18 @@ class Plan:
     def set_mode_shard(self, first, stride, total):
         """The plan's M local Fourier modes stand for the modes first, first + stride, ... of `total`
         (include/rtd.h: rtd_plan_set_mode_shard); evaluators then return this shard's partial sums."""
+        if self._band_active() and (int(first), int(stride), int(total)) != (0, 1, self.M):
+            raise ValueError("a mode shard is not combined with band inputs or band weights.")
         _lib.check(self._lib.rtd_plan_set_mode_shard(self._h, int(first), int(stride), int(total)))
+        self._sharded = (int(first), int(stride), int(total)) != (0, 1, self.M)
         self.solved = False
+
+    def _band_active(self):
+        return self.prep.get("band") is not None or getattr(self, "_band", None) is not None
+
+    def _band_allowed(self):
+        if getattr(self, "_sharded", False) or getattr(self, "_nranks", None) is not None:
+            raise ValueError("band inputs and band weights are not combined with a mode shard or a communicator.")
 
     def allreduce_results(self):
         """RCCL all-reduce (sum) of the results of run() over the ranks of the communicator (mode shards)."""
@@ -122,8 +134,127 @@ class Plan:
                 self._h, _lib.dptr(a["tau_arr"]), _lib.dptr(a["omega_arr"]), _lib.dptr(a["leg"]), a["leg"].shape[2],
                 *[_lib.dptr(a[k]) for k in ("f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")], C.byref(th)))
         # what later checks (set_columns, the closures' tau range, beam terms) compare against follows the new batch
-        self.prep = dict(p, tau=a["tau_arr"], mu0=a["mu0"], phi0=a["phi0"], raw=raw, thermal=_thermal)
+        self.prep = dict(p, tau=a["tau_arr"], mu0=a["mu0"], phi0=a["phi0"], raw=raw, thermal=_thermal, band=None)
         self.solved = False
+
+    def set_columns_band(self, band, cols, thermal=None):
+        """Upload a batch of P profiles x G spectral points as a k-distribution band; tau_arr, omega_arr, f_arr and the moments of
+        the P G columns (column p G + g) are mixed on the device (include/rtd.h: rtd_plan_set_columns_band).
+        band: dict(dtau_abs [P, G, L], dtau_spec [P, L, S], omega_spec [P, L, S], leg_spec [S, nleg_all], delta_m).
+        cols: dict(mu0, I0, phi0 [C], b_pos / b_neg [C, M, N] or None, bdrf_q [C, NBDRF, N, N], bdrf_q0 [C, NBDRF, N] or None).
+        thermal: as in ``set_columns_thermal`` (the plan then needs Ns = 2).  Returns the mixed tau_arr [C, L] as the device formed
+        it.  The C ABI takes bare pointers whose extents the plan implies, so every array's shape is checked here."""
+        self._band_allowed()
+        p = self.prep
+        Cn, L, N, M, Ns, NB = p["C"], p["L"], p["N"], p["M"], p["Ns"], p["NBDRF"]
+        b = {k: _f64(band.get(k)) for k in ("dtau_abs", "dtau_spec", "omega_spec", "leg_spec")}
+        if any(v is None for v in b.values()) or b["dtau_abs"].ndim != 3 or b["dtau_spec"].ndim != 3 or b["leg_spec"].ndim != 2:
+            raise ValueError("band does not match the plan: dtau_abs [P, G, L], dtau_spec and omega_spec [P, L, S] and leg_spec "
+                             "[S, nleg_all] are required")
+        P, G, _ = b["dtau_abs"].shape
+        S, nleg_all = b["leg_spec"].shape
+        delta_m = bool(band.get("delta_m"))
+        if P * G != Cn or b["dtau_abs"].shape != (P, G, L):
+            raise ValueError(f"band does not match the plan: dtau_abs has the shape {b['dtau_abs'].shape}, expected [P, G, {L}] with P G = {Cn}")
+        for k in ("dtau_spec", "omega_spec"):
+            if b[k].shape != (P, L, S) or S < 1:
+                raise ValueError(f"band does not match the plan: {k} has the shape {b[k].shape}, expected {(P, L, S)} with S >= 1")
+        if nleg_all < p["P"] + int(delta_m):
+            raise ValueError(f"band does not match the plan: leg_spec needs {p['P'] + int(delta_m)} moments per species, has {nleg_all}")
+        a = {k: _f64(cols.get(k)) for k in ("mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")}
+        want = {"mu0": (Cn,), "I0": (Cn,), "phi0": (Cn,), "b_pos": (Cn, M, N), "b_neg": (Cn, M, N), "bdrf_q": (Cn, NB, N, N),
+                "bdrf_q0": (Cn, NB, N)}
+        required = {"mu0", "I0", "phi0"} | ({"bdrf_q", "bdrf_q0"} if NB > 0 else set())
+        for k, shape in want.items():
+            if a[k] is None:
+                if k in required:
+                    raise ValueError(f"band batch does not match the plan: {k} is required")
+            elif k.startswith("bdrf") and NB == 0:
+                a[k] = None
+            elif a[k].shape != shape:
+                raise ValueError(f"band batch does not match the plan: {k} has the shape {a[k].shape}, expected {shape}")
+        if not p["beam"] and np.any(a["I0"] > 0):
+            raise ValueError("band batch has a beam source but the plan was created without one")
+        th, keep = None, None
+        if thermal is not None:
+            if Ns != 2:
+                raise ValueError("thermal batch does not match the plan: it needs Ns = 2")
+            twant = {"TEMPER": (Cn, L + 1), "WVNMLO": (Cn,), "WVNMHI": (Cn,), "BTEMP": (Cn,), "TTEMP": (Cn,), "TEMIS": (Cn,),
+                     "emissivity": (Cn, N)}
+            keep = {k: _f64(thermal.get(k)) for k in twant}
+            for k, shape in twant.items():
+                if keep[k] is None:
+                    if k in ("TEMPER", "WVNMLO", "WVNMHI"):
+                        raise ValueError(f"thermal batch does not match the plan: {k} is required")
+                elif keep[k].shape != shape:
+                    raise ValueError(f"thermal batch does not match the plan: {k} has the shape {keep[k].shape}, expected {shape}")
+            th = C.byref(_lib.rtd_thermal(*[_lib.dptr(keep[k]) for k in ("TEMPER", "WVNMLO", "WVNMHI", "BTEMP", "TTEMP", "TEMIS", "emissivity")]))
+        elif Ns != 0:
+            raise ValueError("band batch does not match the plan: a plan with Ns > 0 needs thermal")
+        bs = _lib.rtd_band(P, G, S, nleg_all, int(delta_m), *[_lib.dptr(b[k]) for k in ("dtau_abs", "dtau_spec", "omega_spec", "leg_spec")])
+        tau = np.empty((Cn, L))
+        _lib.check(self._lib.rtd_plan_set_columns_band(
+            self._h, C.byref(bs), *[_lib.dptr(a[k]) for k in ("mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")], th, _lib.dptr(tau)))
+        self.prep = dict(p, tau=tau, mu0=a["mu0"], phi0=a["phi0"], band=band, cols=cols, thermal=thermal, raw=None)
+        self.solved = False
+        return tau
+
+    def set_band_weights(self, weights):
+        """Spectral integration of the results on the device (include/rtd.h: rtd_plan_set_band_weights): weights [K, G], the
+        columns p G ... p G + G - 1 are the spectral points of profile p.  None switches it off."""
+        if weights is None:
+            _lib.check(self._lib.rtd_plan_set_band_weights(self._h, 0, 0, None))
+            self._band = None
+            return
+        self._band_allowed()
+        w = _f64(weights)
+        if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] < 1 or self.C % w.shape[1] != 0:
+            raise ValueError(f"weights must be [K, G] with K >= 1 and G dividing the {self.C} columns of the plan.")
+        _lib.check(self._lib.rtd_plan_set_band_weights(self._h, w.shape[1], w.shape[0], _lib.dptr(w)))
+        self._band = (self.C // w.shape[1], w.shape[0])
+
+    def _band_arrays(self, ntau, nphi, want):
+        if getattr(self, "_band", None) is None:
+            raise ValueError("set_band_weights must precede fetch_band / evaluate_band.")
+        P, K = self._band
+        u = np.empty((P, K, self.Q, ntau, nphi)) if ("u" in want and nphi > 0) else None
+        u0 = np.empty((P, K, self.Q, ntau)) if "u0" in want else None
+        fl = [np.empty((P, K, ntau)) for _ in range(3)] if "flux" in want else [None] * 3
+        return dict(u=u, u0=u0, flux_up=fl[0], flux_down_diffuse=fl[1], flux_down_direct=fl[2])
+
+    def _checked_band(self, rc):
+        """The device has already written NaN into every profile with a failed column: numeric_errors == "nan" only has to keep
+        the status from being raised."""
+        if not (rc == _lib.RTD_ERR_NUMERIC and self.numeric_errors == "nan"):
+            _lib.check(rc)
+
+    def fetch_band(self, want=("u", "u0", "flux")):
+        """After run(): the results at the stored points summed over the spectral points with every weight set, on the device
+        (include/rtd.h: rtd_plan_fetch_band) -> dict(u [P, K, Q, ntau, nphi], u0 [P, K, Q, ntau], flux_up / flux_down_diffuse /
+        flux_down_direct [P, K, ntau]); what `want` leaves out is neither reduced nor copied (None).  A profile with a failed
+        column is NaN (numeric_errors == "nan") or raises NumericalError."""
+        ntau, nphi = self._ev_shape
+        out = self._band_arrays(ntau, nphi, want)
+        self._checked_band(self._lib.rtd_plan_fetch_band(
+            self._h, *[_lib.dptr(out[k]) for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")]))
+        return out
+
+    def evaluate_band(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
+        """``evaluate`` without copying the unreduced fields out: tau [C, ntau] (the t-th point of each of a profile's columns must
+        be the same physical level), phi [nphi] or None -> the dict of ``fetch_band`` (include/rtd.h: rtd_plan_evaluate_band)."""
+        if antiderivative and derivative:
+            raise ValueError("antiderivative and derivative exclude each other.")
+        tau = _f64(np.atleast_2d(tau))
+        assert tau.shape[0] == self.C
+        ntau = tau.shape[1]
+        phi = _f64(np.atleast_1d(phi)) if phi is not None else None
+        nphi = 0 if phi is None else len(phi)
+        out = self._band_arrays(ntau, nphi, want)
+        self._ev_shape = (ntau, nphi)
+        self._checked_band(self._lib.rtd_plan_evaluate_band(
+            self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi), int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0),
+            *[_lib.dptr(out[k]) for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")]))
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -322,6 +453,8 @@ class Plan:
         return buf.raw
 
     def comm_init(self, uid, rank, nranks):
+        if self._band_active():
+            raise ValueError("a communicator is not combined with band inputs or band weights.")
         _lib.check(self._lib.rtd_comm_init(self._h, uid, rank, nranks))
         self._nranks = nranks
 
@@ -443,6 +576,27 @@ def planck_band(T, WVNMLO, WVNMHI, device=0):
     out = np.empty(T.shape)
     _lib.check(_lib.load().rtd_planck_band(int(device), out.size, _lib.dptr(t), _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(out)))
     return out[()]
+
+
+def band_mix(dtau_abs, dtau_spec, omega_spec, Leg_spec, NLeg, delta_M=True, device=0):
+    """The effective optical properties of a k-distribution band, mixed on the device as ``pydisort_band`` mixes them
+    (include/rtd.h: rtd_band_mix): dtau_abs [P, G, L], dtau_spec and omega_spec [P, L, S], Leg_spec [S, nleg_all] ->
+    (tau_arr, omega_arr, f_arr [P G, L], Leg_coeffs [P G, L, NLeg]), column p G + g.  f_arr is the mixture's moment NLeg with
+    delta_M, else 0; a layer without a scatterer has the moments (1, 0, ...)."""
+    a, ds, om, leg = (_f64(v) for v in (dtau_abs, dtau_spec, omega_spec, Leg_spec))
+    if a.ndim != 3 or ds.ndim != 3 or leg.ndim != 2:
+        raise ValueError("band_mix: need dtau_abs [P, G, L], dtau_spec and omega_spec [P, L, S] and Leg_spec [S, nleg_all].")
+    P, G, L = a.shape
+    S, nleg_all = leg.shape
+    if ds.shape != (P, L, S) or om.shape != (P, L, S):
+        raise ValueError(f"band_mix: dtau_spec and omega_spec must have the shape {(P, L, S)}.")
+    NLeg = int(NLeg)
+    if NLeg < 1 or nleg_all < NLeg + int(bool(delta_M)):
+        raise ValueError("band_mix: Leg_spec needs NLeg moments per species, and one more with delta_M.")
+    bs = _lib.rtd_band(P, G, S, nleg_all, int(bool(delta_M)), *[_lib.dptr(v) for v in (a, ds, om, leg)])
+    out = [np.empty((P * G, L)) for _ in range(3)] + [np.empty((P * G, L, NLeg))]
+    _lib.check(_lib.load().rtd_band_mix(int(device), L, NLeg, C.byref(bs), *[_lib.dptr(v) for v in out]))
+    return tuple(out)
 
 
 def device_count():

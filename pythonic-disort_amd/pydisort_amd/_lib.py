@@ -31,6 +31,12 @@ class rtd_thermal(C.Structure):
     _fields_ = [(n, _dp) for n in ("temper", "wvnmlo", "wvnmhi", "btemp", "ttemp", "temis", "emissivity")]
 
 
+class rtd_band(C.Structure):
+    """A k-distribution band for rtd_band_mix / rtd_plan_set_columns_band (include/rtd.h: rtd_band)."""
+    _fields_ = [(n, C.c_int32) for n in ("nprofiles", "ngpoints", "nspecies", "nleg_all", "delta_m")] + \
+               [(n, _dp) for n in ("dtau_abs", "dtau_spec", "omega_spec", "leg_spec")]
+
+
 # every symbol include/rtd.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "rtd_version": (C.c_int, []),
@@ -55,6 +61,11 @@ SIGNATURES = {
     "rtd_plan_set_columns_raw": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 9),
     "rtd_plan_set_columns_thermal": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8 + [C.POINTER(rtd_thermal)]),
     "rtd_planck_band": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp]),
+    "rtd_band_mix": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(rtd_band)] + [_dp] * 4),
+    "rtd_plan_set_columns_band": (C.c_int, [_vp, C.POINTER(rtd_band)] + [_dp] * 7 + [C.POINTER(rtd_thermal), _dp]),
+    "rtd_plan_set_band_weights": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp]),
+    "rtd_plan_fetch_band": (C.c_int, [_vp] + [_dp] * 5),
+    "rtd_plan_evaluate_band": (C.c_int, [_vp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32] + [_dp] * 5),
     "rtd_plan_set_bdrf_samples": (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     "rtd_plan_set_mode_shard": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "rtd_plan_invalidate_tables": (C.c_int, [_vp]),

@@ -1,0 +1,258 @@
+"""k-distribution bands: P profiles x G spectral points per call, mixed and spectrally integrated on the device (no reference
+equivalent -- the reference solves one monochromatic column per ``pydisort`` call).
+
+Within a band every column of a profile shares its scatterers, its geometry and its surface; only the gas absorption per layer and
+the solar weight change from point to point, and what is wanted back is P band results, not P G monochromatic ones.  The band is
+stated as the user has it -- G + 2 S numbers per profile and layer -- and the device forms tau_arr, omega_arr, f_arr and the
+Legendre moments of the P G columns (include/rtd.h: rtd_plan_set_columns_band) and sums the results over g with the band's
+weights (rtd_plan_set_band_weights).  Column p G + g throughout."""
+import numpy as np
+
+from ._engine import Plan
+from ._prepare import double_gauss
+from .batch import BatchSolution, _retention, _thermal_inputs
+
+
+def level_tau(tau_arr, levels=None):
+    """The optical depth of the interfaces `levels` (indices 0 ... L, None: all of them) of every column: tau_arr [C, L] ->
+    [C, nlev].  A level is the only coordinate the spectral points of a profile share: each column is evaluated at its OWN
+    optical depth of that level."""
+    tau_arr = np.asarray(tau_arr, float)
+    C, L = tau_arr.shape
+    table = np.concatenate((np.zeros((C, 1)), tau_arr), axis=1)
+    if levels is None:
+        return table
+    lv = np.atleast_1d(np.asarray(levels))
+    if lv.ndim != 1 or lv.size < 1 or not np.issubdtype(lv.dtype, np.integer):
+        raise ValueError("levels must be interface indices (integers), a scalar or a one-dimensional sequence.")
+    if np.any(lv < 0) or np.any(lv > L):
+        raise ValueError(f"levels must lie between 0 and the number of layers ({L}).")
+    return np.ascontiguousarray(table[:, lv])
+
+
+def net_flux_convergence(flux_up, flux_down_diffuse, flux_down_direct):
+    """F_net[l] - F_net[l + 1] with F_net = down_diffuse + down_direct - up at ALL levels [..., L + 1] -> [..., L]: the power
+    each layer absorbs, the heating rate up to the caller's units."""
+    net = np.asarray(flux_down_diffuse, float) + np.asarray(flux_down_direct, float) - np.asarray(flux_up, float)
+    return net[..., :-1] - net[..., 1:]
+
+
+def _per_column(v, name, P, G, tail=()):
+    """A boundary / surface / thermal array given per profile [P, ...] or per column [P G, ...] -> per column."""
+    v = np.asarray(v, float)
+    C = P * G
+    if v.shape == (C,) + tail:
+        return v
+    if v.shape == (P,) + tail:
+        return np.repeat(v, G, axis=0)
+    raise ValueError(f"{name} must be given per profile {(P,) + tail} or per column {(C,) + tail}; got {v.shape}.")
+
+
+def _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg, NFourier, delta_M, only_flux,
+                 b_pos, b_neg, bdrf_q, bdrf_q0, thermal):
+    """Everything a user can get wrong is raised here, on the small arrays, before anything touches the device.
+    -> (prep for ``Plan``, weights [K, G], whether the K axis is dropped)."""
+    a, ds, om, leg = (np.asarray(v, float) for v in (dtau_abs, dtau_spec, omega_spec, Leg_spec))
+    if a.ndim != 3:
+        raise ValueError("dtau_abs must have the shape [P, G, L].")
+    P, G, L = a.shape
+    if ds.ndim != 3 or ds.shape[:2] != (P, L) or ds.shape[2] < 1:
+        raise ValueError(f"dtau_spec must have the shape [P = {P}, L = {L}, S] with at least one species.")
+    S = ds.shape[2]
+    if om.shape != (P, L, S):
+        raise ValueError(f"omega_spec must have the shape of dtau_spec {(P, L, S)}.")
+    if leg.ndim != 2 or leg.shape[0] != S:
+        raise ValueError(f"Leg_spec must have the shape [S = {S}, NLeg_all].")
+    N = NQuad // 2
+    NLeg = NQuad if NLeg is None else NLeg
+    NFourier = 1 if only_flux else (NQuad if NFourier is None else NFourier)
+    if NQuad % 2 or NQuad < 2 or NQuad > 128:
+        raise ValueError("NQuad must be even and between 2 and 128.")
+    if not (0 < NFourier <= NLeg <= NQuad and NLeg <= leg.shape[1]):
+        raise ValueError("Need 0 < NFourier <= NLeg <= NQuad and NLeg <= number of Legendre coefficients provided.")
+    if delta_M and leg.shape[1] <= NLeg:
+        raise ValueError("delta_M needs more Legendre coefficients per species than NLeg (the truncation fraction is moment NLeg).")
+    if not (np.all(a >= 0) and np.all(ds >= 0)):
+        raise ValueError("Optical thicknesses (dtau_abs, dtau_spec) must not be negative.")
+    if not (np.all(om >= 0) and np.all(om <= 1)):
+        raise ValueError("Single-scattering albedo of every species must be between 0 and 1.")
+    if not np.all(leg[:, 0] == 1):
+        raise ValueError("The zeroth Legendre coefficient of every species must be 1.")
+    # every (p, g, l) through the spectral point of least absorption: never by forming the columns
+    least = ds.sum(axis=2) + a.min(axis=1)
+    if not np.all(least > 0):
+        raise ValueError("Every layer must have a positive optical thickness at every spectral point.")
+    if not np.all((om * ds).sum(axis=2) < least):
+        raise ValueError("Single-scattering albedo of the mixture must be between 0 and 1, excluding 1.")
+    w = np.asarray(weights, float)
+    squeeze = w.ndim == 1
+    if w.ndim not in (1, 2) or w.shape[-1] != G or w.size == 0:
+        raise ValueError(f"weights must have the shape [G = {G}] or [K, G].")
+    w = np.ascontiguousarray(np.atleast_2d(w))
+    C = P * G
+
+    def per_profile(v, name):
+        v = np.asarray(v, float)
+        if v.ndim == 0 or v.shape == (P,):
+            return np.repeat(np.broadcast_to(v, (P,)), G)
+        raise ValueError(f"{name} must be a scalar or [P = {P}].")
+
+    mu0c, phi0c = per_profile(mu0, "mu0"), per_profile(phi0, "phi0")
+    I0 = np.asarray(I0, float)
+    if I0.ndim == 0 or I0.shape == (G,) or I0.shape == (P, G):  # (P = G: a vector is taken per spectral point)
+        I0c = np.ascontiguousarray(np.broadcast_to(I0, (P, G))).reshape(C)
+    elif I0.shape == (P,):
+        I0c = np.repeat(I0, G)
+    else:
+        raise ValueError(f"I0 must be a scalar, [G = {G}], [P = {P}] or [P, G].")
+    if np.any(I0c < 0) or (np.any(I0c > 0) and not np.all((mu0c > 0) & (mu0c <= 1))):
+        raise ValueError("Need I0 >= 0 and 0 < mu0 <= 1 for every column when there is a beam source.")
+
+    def bc(b, name):
+        b = np.asarray(b, float)
+        if b.ndim == 0:
+            if b == 0:
+                return None  # all zero: nothing to allocate or upload
+            b = np.broadcast_to(b, (P,))
+        out = np.zeros((C, NFourier, N))
+        if b.ndim == 1:
+            out[:, 0, :] = _per_column(b, name, P, G)[:, None]
+        elif b.ndim == 2:
+            out[:, 0, :] = _per_column(b, name, P, G, (N,))
+        elif b.ndim == 3:
+            out[:] = _per_column(b, name, P, G, (N, NFourier)).transpose(0, 2, 1)
+        else:
+            raise ValueError("The shape of a boundary condition is incorrect.")
+        return out
+
+    bp, bn = bc(b_pos, "b_pos"), bc(b_neg, "b_neg")
+    if (bdrf_q is None) != (bdrf_q0 is None):
+        raise ValueError("Give bdrf_q and bdrf_q0 together.")
+    NB, bq, bq0 = 0, None, None
+    if bdrf_q is not None:
+        bq = np.asarray(bdrf_q, float)
+        if bq.ndim != 4 or bq.shape[2:] != (N, N) or not 0 < bq.shape[1] <= NFourier:
+            raise ValueError("bdrf_q must have the shape [P or P G, NBDRF <= NFourier, N, N].")
+        NB = bq.shape[1]
+        bq = np.ascontiguousarray(_per_column(bq, "bdrf_q", P, G, (NB, N, N)))
+        bq0 = np.ascontiguousarray(_per_column(bdrf_q0, "bdrf_q0", P, G, (NB, N)))
+    th = None
+    if thermal is not None:
+        t = dict(thermal)
+        for k, v in list(t.items()):
+            if v is None or np.ndim(v) == 0 or (k == "TEMPER" and np.ndim(v) == 1):
+                continue
+            tail = (L + 1,) if k == "TEMPER" else (N,) if (k == "emissivity" and np.ndim(v) == 2) else ()
+            t[k] = _per_column(v, "thermal: " + k, P, G, tail)
+        th = _thermal_inputs(t, C, L, N, False)
+    mu, W = double_gauss(N)
+    band = dict(dtau_abs=a, dtau_spec=ds, omega_spec=om, leg_spec=leg, delta_m=bool(delta_M))
+    cols = dict(mu0=mu0c, I0=I0c, phi0=phi0c, b_pos=bp, b_neg=bn, bdrf_q=bq, bdrf_q0=bq0)
+    prep = dict(C=C, L=L, N=N, P=NLeg, M=NFourier, Ns=2 if th is not None else 0, NBDRF=NB, beam=bool(np.any(I0c > 0)), mu=mu, W=W,
+                tau=None, raw=None, band=band, cols=cols, thermal=th)
+    return prep, w, squeeze
+
+
+class BandSolution:
+    """Band results of P profiles: every evaluator returns [P, K, ...], summed over the G spectral points with each of the K
+    weight sets on the device (the K axis is dropped when ``weights`` was [G]).  ``levels`` are interface indices 0 ... L (None:
+    all of them); each column is evaluated at its own optical depth of the level.
+
+    columns : the ordinary ``BatchSolution`` over the P G columns (unreduced evaluators in tau, column p G + g).
+    tau_arr : [P, G, L] the mixed optical depths of the lower layer boundaries, as the device formed them."""
+
+    def __init__(self, plan, P, G, squeeze):
+        self.plan, self.P, self.G, self._squeeze = plan, P, G, squeeze
+        self.columns = BatchSolution(plan, plan.prep)
+        self.mu_arr = self.columns.mu_arr
+        self.tau_arr = plan.prep["tau"].reshape(P, G, -1)
+
+    def _out(self, a):
+        return a[:, 0] if self._squeeze else a
+
+    def _eval(self, levels, phi, want):
+        return self.plan.evaluate_band(level_tau(self.plan.prep["tau"], levels), phi, want=want)
+
+    def flux_up(self, levels=None):
+        """-> [P, K, nlev]"""
+        return self._out(self._eval(levels, None, ("flux",))["flux_up"])
+
+    def flux_down(self, levels=None):
+        """-> (diffuse [P, K, nlev], direct [P, K, nlev])"""
+        r = self._eval(levels, None, ("flux",))
+        return self._out(r["flux_down_diffuse"]), self._out(r["flux_down_direct"])
+
+    def u0(self, levels=None):
+        """-> [P, K, NQuad, nlev]"""
+        return self._out(self._eval(levels, None, ("u0",))["u0"])
+
+    def u(self, levels, phi):
+        """-> [P, K, NQuad, nlev, nphi]"""
+        return self._out(self._eval(levels, phi, ("u",))["u"])
+
+    def net_flux_convergence(self):
+        """-> [P, K, L]: F_net[l] - F_net[l + 1], F_net = down_diffuse + down_direct - up: the layers' absorbed power (host
+        arithmetic on the reduced level fluxes)."""
+        r = self._eval(None, None, ("flux",))
+        return self._out(net_flux_convergence(r["flux_up"], r["flux_down_diffuse"], r["flux_down_direct"]))
+
+
+def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=None, NFourier=None,
+                  delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None, bdrf_q0=None, thermal=None, device=0,
+                  work_columns=0, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False):
+    """P profiles x G spectral points of a band in one call.
+
+    dtau_abs [P, G, L]: absorption optical thickness of each layer at each spectral point; dtau_spec, omega_spec [P, L, S]:
+    extinction optical thickness and single-scattering albedo of each of S scatterer species; Leg_spec [S, NLeg_all]: the species'
+    Legendre coefficients.  The device mixes them into the P G columns (column p G + g):
+    dtau = sum_s dtau_s + dtau_abs, omega = sum_s omega_s dtau_s / dtau, moments weighted by omega_s dtau_s; with delta_M the
+    truncation fraction f is the mixture's moment NLeg (Leg_spec then needs more than NLeg moments).  A layer without a scatterer
+    gets the moments (1, 0, ...).
+    mu0, phi0: scalar or [P]; I0: scalar, [G] (the solar weight of each spectral point), [P] or [P, G].
+    weights: [G] or [K, G] -- k-distribution weights, several channels' response functions, photolysis cross sections.
+    b_pos / b_neg (scalar, [.], [., N] or [., N, NFourier]), bdrf_q [., NBDRF, N, N], bdrf_q0 [., NBDRF, N] and the arrays of
+    ``thermal`` (as in ``pydisort_batch``) are per profile, or per column where they differ by g.
+    Everything else as in ``pydisort_batch``.  Not combined with NT corrections, mode shards or communicators.
+    Returns (mu_arr, BandSolution)."""
+    prep, w, squeeze = _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg, NFourier, delta_M,
+                                    only_flux, b_pos, b_neg, bdrf_q, bdrf_q0, thermal)
+    if numeric_errors not in ("raise", "nan"):
+        raise ValueError('numeric_errors must be "raise" or "nan".')
+    form, budget = _retention(retain, retain_bytes, _defer_solve, prep["C"], prep["N"], prep["M"], prep["L"], device)
+    plan = Plan(prep, device=device, work_columns=work_columns, retain_bytes=budget, retain_form=form or 0)
+    plan.numeric_errors = numeric_errors
+    plan.set_band_weights(w)
+    if not _defer_solve:
+        plan.solve()
+    G = w.shape[1]
+    sol = BandSolution(plan, prep["C"] // G, G, squeeze)
+    return sol.mu_arr, sol
+
+
+def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, levels=None, phi=None,
+                        chunk_columns=0, NLeg=None, NFourier=None, delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None,
+                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise"):
+    """Throughput form of ``pydisort_band`` (as ``solve_columns_streamed`` is of ``pydisort_batch``): ONE plan holds the inputs
+    and the results of all P G columns, the intermediates of the solve live for `chunk_columns` columns at a time, the results at
+    `levels` (None: all L + 1) and `phi` are reduced on the device and only the P band results travel to the host -- 1 / G of what
+    ``Plan.run_fetch`` moves, so no window-overlapped copy is needed.
+    Returns dict(u [P, K, NQuad, nlev, nphi] (absent when only_flux), u0 [P, K, NQuad, nlev], flux_up, flux_down_diffuse,
+    flux_down_direct [P, K, nlev], tau_arr [P, G, L]); the K axis is dropped when ``weights`` was [G]."""
+    if chunk_columns <= 0:  # (as solve_columns_streamed: windows of ~8 192 (column, mode) chains)
+        modes = 1 if only_flux else int(NFourier or NLeg or NQuad)
+        chunk_columns = max(64, 8192 // max(modes, 1))
+    _, sol = pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=NLeg, NFourier=NFourier,
+                           delta_M=delta_M, only_flux=only_flux, b_pos=b_pos, b_neg=b_neg, bdrf_q=bdrf_q, bdrf_q0=bdrf_q0,
+                           thermal=thermal, device=device, work_columns=chunk_columns, numeric_errors=numeric_errors, retain=False,
+                           _defer_solve=True)
+    plan = sol.plan
+    try:
+        phi = np.array([0.0]) if (only_flux or phi is None) else np.atleast_1d(np.asarray(phi, float))
+        plan.set_eval_points(level_tau(plan.prep["tau"], levels), phi)
+        plan.run()
+        out = plan.fetch_band(want=("u0", "flux") if only_flux else ("u", "u0", "flux"))
+    finally:
+        plan.close()
+    out = {k: sol._out(v) for k, v in out.items() if v is not None}
+    out["tau_arr"] = sol.tau_arr
+    return out

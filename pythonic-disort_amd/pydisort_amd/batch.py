@@ -59,6 +59,28 @@ def _thermal_inputs(thermal, C, L, N, with_bdrf_samples):
     return out
 
 
+def _retention(retain, retain_bytes, defer_solve, C, N, NFourier, L, device):
+    """``retain`` / ``retain_bytes`` of ``pydisort_batch`` -> (form, budget in bytes) for ``Plan``."""
+    form = {"auto": 0, True: 0, "full": 1, "lean": 2}.get(retain if isinstance(retain, (str, bool)) else "auto")
+    if retain is False or retain is None or (retain == "auto" and defer_solve):
+        budget = 0  # (the throughput callers drive plan.run() themselves: nothing to keep)
+    elif form is None:
+        raise ValueError('retain must be "auto", "full", "lean", False or a number of bytes.')
+    elif isinstance(retain, (int, np.integer)) and not isinstance(retain, bool):
+        budget = int(retain)  # (an int: that many bytes, the round-5 spelling of retain_bytes)
+    else:
+        budget = DEFAULT_RETAIN_BYTES if retain_bytes is None else int(retain_bytes)
+        if budget > 0 and retain_bytes is None:
+            # the default never takes more than three tenths of what is free -- asked of the runtime only when the batch is large
+            # enough for it to matter (hipMemGetInfo costs a small call a noticeable fraction of its time)
+            NP = 4
+            while NP < N:
+                NP *= 2
+            if C * NFourier * L * (2 * NP * NP + 8 * NP) * 8 > (256 << 20):
+                budget = max(1, min(budget, int(0.3 * Plan.free_device_bytes(device))))
+    return form, budget
+
+
 class BatchSolution:
     """Evaluators over all columns; arrays carry a leading column axis.
 
@@ -235,23 +257,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
         NT_cor = NT_cor and r == 0
     if numeric_errors not in ("raise", "nan"):
         raise ValueError('numeric_errors must be "raise" or "nan".')
-    form = {"auto": 0, True: 0, "full": 1, "lean": 2}.get(retain if isinstance(retain, (str, bool)) else "auto")
-    if retain is False or retain is None or (retain == "auto" and _defer_solve):
-        budget = 0  # (the throughput callers drive plan.run() themselves: nothing to keep)
-    elif form is None:
-        raise ValueError('retain must be "auto", "full", "lean", False or a number of bytes.')
-    elif isinstance(retain, (int, np.integer)) and not isinstance(retain, bool):
-        budget = int(retain)  # (an int: that many bytes, the round-5 spelling of retain_bytes)
-    else:
-        budget = DEFAULT_RETAIN_BYTES if retain_bytes is None else int(retain_bytes)
-        if budget > 0 and retain_bytes is None:
-            # the default never takes more than three tenths of what is free -- asked of the runtime only when the batch is large
-            # enough for it to matter (hipMemGetInfo costs a small call a noticeable fraction of its time)
-            NP = 4
-            while NP < N:
-                NP *= 2
-            if C * NFourier * L * (2 * NP * NP + 8 * NP) * 8 > (256 << 20):
-                budget = max(1, min(budget, int(0.3 * Plan.free_device_bytes(device))))
+    form, budget = _retention(retain, retain_bytes, _defer_solve, C, N, NFourier, L, device)
     plan = Plan(prep, device=device, work_columns=work_columns, retain_bytes=budget, retain_form=form or 0)
     plan.numeric_errors = numeric_errors
     if bdrf_samples is not None:
