@@ -315,7 +315,36 @@ int rtd_plan_fetch_band(rtd_plan* plan, double* u, double* u0, double* flux_up, 
  * unreduced fields out: evaluates into the device buffers, reduces, returns the reduced arrays of rtd_plan_fetch_band. */
 int rtd_plan_evaluate_band(rtd_plan* plan, int32_t ntau, const double* tau, int32_t nphi, const double* phi, int32_t flags,
                            double* u, double* u0, double* flux_up, double* flux_down_diffuse, double* flux_down_direct);
-/* device pointers of the result buffers of rtd_plan_run (for a device-side collective) */
+/* Actinic fluxes (4 pi x the mean intensity: what a photolysis rate integrates) of the results the plan holds, formed on the
+ * device from the resident u0 (rtd_actinic_kernel, one thread per column and point, the streams summed in ascending order: the
+ * bits depend on neither the launch geometry nor the window size).  The reference has them for one column on the host
+ * (generate_diff_act_flux_funcs, subroutines.py:258-318; _assemble_intensity_and_fluxes.py:353-371).  With x = u0, w the
+ * quadrature weights, l, tau* and sc = scale_tau[l] of the point as in rtd_plan_evaluate, and I0 the CALLER's beam
+ * (rescale x the prepared I0):
+ *   act_up           = 2 pi sum_{i<N} w_i x_i
+ *   act_down_diffuse = 2 pi sum_{i<N} w_i x_{N+i} + R,   R = I0 e^(-tau* / mu0) - I0 e^(-tau / mu0)
+ *   act_down_direct  = D = I0 e^(-tau / mu0)             (flux_down_direct / mu0; no counterpart in the reference)
+ * in the order (value, tau-antiderivative, tau-derivative) the results were evaluated in -- rtd_plan_set_eval_order for
+ * rtd_plan_run / _run_fetch, the flag word for rtd_plan_evaluate / _evaluate_band:
+ *   antiderivative: R = I0 e^(-tau* / mu0) / (-sc / mu0) - I0 e^(-tau / mu0) (-mu0),   D = I0 e^(-tau / mu0) (-mu0)
+ *   derivative:     R = I0 e^(-tau* / mu0) (-sc / mu0) - I0 e^(-tau / mu0) / (-mu0),   D = I0 e^(-tau / mu0) / (-mu0)
+ * R is the part of the direct beam that delta-M scaling reclassifies as diffuse: act_down_diffuse + act_down_direct is the
+ * physical downward actinic flux.  R = D = 0 for a plan without a beam and for a column with I0 = 0; a mode shard that does not
+ * own mode 0 returns zeros, like the fluxes.  (The reference forms R with the I0 it has divided by its rescale factor and does
+ * not multiply back: its flux_act_down_diffuse is low by R (1 - 1 / rescale) whenever another source exceeds the beam.)
+ * [C][ntau] each, ntau that of the LATEST evaluation (rtd_plan_evaluate / _evaluate_band replace the stored points, whatever
+ * outputs they were asked for; flux_bytes of rtd_plan_result_dev_ptrs = 3 C ntau 8 tells it); any pointer may be NULL.
+ * RTD_ERR_STATE when the plan holds no evaluated results (nothing solved, or new evaluation points, new inputs, a new mode shard
+ * or a new solve -- rtd_plan_solve or the layer-shard pair -- since); RTD_ERR_NUMERIC as rtd_plan_fetch reports it for u0.
+ * The buffers behind these calls are allocated at the first of them: a plan that never asks holds what it held before.  The
+ * gathered-results collectives (rtd_comm_*) do not carry actinic fluxes. */
+int rtd_plan_fetch_actinic(rtd_plan* plan, double* act_up, double* act_down_diffuse, double* act_down_direct);
+/* The same summed over the spectral points with every weight set (rtd_plan_set_band_weights; rtd_band_reduce_kernel with the
+ * mode-0 mask), [P][K][ntau]: with w[k][g] = cross section x quantum yield x the point's k-weight, up + diffuse + direct is the
+ * photolysis rate per level.  RTD_ERR_STATE without weights; a profile with a failed column is NaN and the call returns
+ * RTD_ERR_NUMERIC, as rtd_plan_fetch_band. */
+int rtd_plan_fetch_band_actinic(rtd_plan* plan, double* act_up, double* act_down_diffuse, double* act_down_direct);
+/* device pointers of the result buffers of rtd_plan_run (for a device-side collective); any pointer may be NULL */
 int rtd_plan_result_dev_ptrs(rtd_plan* plan, void** u_dev, int64_t* u_bytes, void** flux_dev, int64_t* flux_bytes);
 
 /* --- the reference's tensors for one column (layout of the reference) ---------------------- */

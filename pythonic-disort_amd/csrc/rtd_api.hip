@@ -325,6 +325,13 @@ struct rtd_plan {
   int band_G = 0, band_K = 0;
   double *band_w = nullptr, *rb_u = nullptr, *rb_u0 = nullptr, *rb_fl = nullptr;
   int64_t cap_band_w = 0, cap_rb_u = 0, cap_rb_u0 = 0, cap_rb_fl = 0;
+  // actinic fluxes (rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic): res_order is the order (-1 / 0 / +1) the resident
+  // results were evaluated in, RES_NONE while the buffers hold no evaluation of the stored points; ev_act [3][C][ntau] and the
+  // reduced rb_act [3][P][K][ntau] are grown at the first actinic fetch, so a plan that never asks holds nothing more
+  static constexpr int RES_NONE = 2;
+  int res_order = RES_NONE;
+  double *ev_act = nullptr, *rb_act = nullptr;
+  int64_t cap_act = 0, cap_rb_act = 0;
   // export buffers
   double* ex_buf = nullptr;
   // Nakajima-Tanaka corrections (optional)
@@ -707,7 +714,7 @@ extern "C" {
 
 int rtd_comm_destroy(rtd_plan* p);
 
-int rtd_version(void) { return 213; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band
+int rtd_version(void) { return 214; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic
 
 const char* rtd_last_error(void) { return g_err.c_str(); }
 
@@ -1059,6 +1066,7 @@ int rtd_plan_set_quadrature(rtd_plan* p, const double* mu_pos, const double* wei
   p->quad_tables_valid = false;
   p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read the nodes)
   p->solved = false;
+  p->res_order = rtd_plan::RES_NONE;
   return 0;
 }
 
@@ -1174,6 +1182,7 @@ int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* 
   p->tables_valid = false;
   p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read taus0, scale and mu0 of the batch)
   p->solved = false;
+  p->res_order = rtd_plan::RES_NONE;
   return 0;
 }
 
@@ -1368,6 +1377,60 @@ __global__ void rtd_band_reduce_kernel(const double* X, const double* w, const i
   }
 }
 
+// Actinic fluxes (4 pi x mean intensity) of the results the plan holds: the reference's generate_diff_act_flux_funcs
+// (subroutines.py:258-318) for every column and point at once.  One thread per (column c, point t), lanes along t, then c: for
+// each stream i a wavefront reads runs of ntau consecutive doubles of u0 [C][2N][ntau].  The sum over the streams is one chain, i
+// ascending, no atomics: the bits depend on nothing but the inputs.  x = u0 carries `rescale` already; I0 here is the CALLER's
+// beam, rescale * d.I0 (pydisort.py:311-326) -- the reference applies the reclassification term R with its rescaled I0 and does not
+// multiply back.  order: -1 the tau-antiderivative, 0 the value, +1 the tau-derivative, the order u0 was
+// evaluated in; layer lookup and one-sided conventions as rtd_eval_kernel's.
+//   act [0][c][t] = 2 pi sum_i w_i x_i               (up)
+//   act [1][c][t] = 2 pi sum_i w_i x_{N+i} + R       (down, diffuse; R = I0 e^(-tau* / mu0) - I0 e^(-tau / mu0))
+//   act [2][c][t] = D = I0 e^(-tau / mu0)            (down, direct: flux_down_direct / mu0)
+// R = D = 0 without a beam and where I0 = 0; everything is 0 on a mode shard that does not own mode 0.
+__global__ void rtd_actinic_kernel(RtdDev d, const double* ev_tau, const double* u0, int ntau, int order, double* act) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x, CT = (long)d.C * ntau;
+  if (idx >= CT) return;
+  const long c = idx / ntau;
+  const int t = (int)(idx % ntau), L = d.L, N = d.N;
+  double up = 0.0, dn = 0.0, R = 0.0, D = 0.0;
+  if (d.m0 == 0) {
+    const double* x = u0 + c * 2 * N * ntau + t;
+    for (int i = 0; i < N; ++i) {
+      up += d.w[i] * x[(long)i * ntau];
+      dn += d.w[i] * x[(long)(N + i) * ntau];
+    }
+    up *= 2.0 * M_PI;
+    dn *= 2.0 * M_PI;
+    const double I0 = d.beam ? d.rescale[c] * d.I0[c] : 0.0;
+    if (I0 != 0.0) {
+      const double tau = ev_tau[idx], mu0 = d.mu0[c];
+      const double* tau_arr = d.tau + c * L;
+      int l = 0;
+      // argmax(tau <= tau_arr), always by search.  The fused evaluation behind rtd_plan_run takes l = t - 1 at the interfaces
+      // instead (rtd_eval.hip, rtd_fourier.hip); the two agree unless a layer has zero thickness (tau_arr[l] == tau_arr[l + 1]).
+      // There tau* and so the value order are the same under either rule, but sc of the derivative and antiderivative factors
+      // below is the upper layer's, while the resident u0 they are added to was formed with the empty layer's.
+      while (l < L - 1 && !(tau <= tau_arr[l])) ++l;
+      const double sc = d.scale[c * L + l];
+      const double ts = d.taus0[c * (L + 1) + l + 1] - (tau_arr[l] - tau) * sc;
+      double es = I0 * exp(-ts / mu0), ed = I0 * exp(-tau / mu0);
+      if (order < 0) {
+        es /= (-sc / mu0);
+        ed *= -mu0;
+      } else if (order > 0) {
+        es *= (-sc / mu0);
+        ed /= -mu0;
+      }
+      R = es - ed;
+      D = ed;
+    }
+  }
+  act[idx] = up;
+  act[CT + idx] = dn + R;
+  act[2 * CT + idx] = D;
+}
+
 }  // namespace
 
 int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wvnmlo, const double* wvnmhi, double* out) {
@@ -1537,6 +1600,7 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   p->tables_valid = false;
   p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read taus0, scale and mu0 of the batch)
   p->solved = false;
+  p->res_order = rtd_plan::RES_NONE;
   return 0;
 }
 
@@ -1624,6 +1688,7 @@ int rtd_plan_set_bdrf_samples(rtd_plan* p, int32_t nphi, const double* rho_qq, c
   (void)hipFree(tmp);
   if (e != hipSuccess) return fail(RTD_ERR_HIP, hipGetErrorString(e));
   p->solved = false;
+  p->res_order = rtd_plan::RES_NONE;
   return 0;
 }
 
@@ -1639,6 +1704,7 @@ int rtd_plan_set_mode_shard(rtd_plan* p, int32_t first, int32_t stride, int32_t 
   d.mstep = stride;
   d.mtot = total;
   p->solved = false;
+  p->res_order = rtd_plan::RES_NONE;
   p->tables_valid = false;
   p->quad_tables_valid = false;
   return 0;
@@ -1656,6 +1722,7 @@ int rtd_plan_solve(rtd_plan* p) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
   if (!p->have_quad || !p->have_cols) return fail(RTD_ERR_STATE, "set_quadrature and set_columns must precede solve");
   HIP_TRY(hipSetDevice(p->device));
+  p->res_order = rtd_plan::RES_NONE;  // (what the result buffers hold belongs to an earlier solve)
   return launch_solve(p, false, nullptr);
 }
 
@@ -1664,6 +1731,7 @@ int rtd_plan_set_eval_points(rtd_plan* p, int32_t ntau, const double* tau, int32
   HIP_TRY(hipSetDevice(p->device));
   const int64_t C = p->d.C, Qr = 2 * p->d.N;
   int rc;
+  p->res_order = rtd_plan::RES_NONE;  // (the result buffers hold no evaluation at these points yet)
   if ((rc = grow(p, &p->ev_tau, &p->cap_tau, C * ntau))) return rc;
   if ((rc = grow(p, &p->ev_phi, &p->cap_phi, nphi > 0 ? nphi : 1))) return rc;
   if ((rc = grow(p, &p->ev_u, &p->cap_u, C * Qr * ntau * (nphi > 0 ? nphi : 1)))) return rc;
@@ -1721,7 +1789,9 @@ int rtd_plan_run(rtd_plan* p) {
   if (!p->have_quad || !p->have_cols || p->ev_ntau < 1) return fail(RTD_ERR_STATE, "inputs or evaluation points missing");
   HIP_TRY(hipSetDevice(p->device));
   RtdEval e = make_eval(p, p->eval_order, true);
-  return launch_solve(p, true, &e, p->have_nt);
+  int rc = launch_solve(p, true, &e, p->have_nt);
+  p->res_order = rc ? rtd_plan::RES_NONE : p->eval_order;
+  return rc;
 }
 
 int rtd_plan_set_eval_order(rtd_plan* p, int32_t order) {
@@ -1799,6 +1869,7 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
     return 0;
   };
   RtdEval e = make_eval(p, p->eval_order, true);
+  p->res_order = rtd_plan::RES_NONE;
   int rc = launch_windows(p, true, &e, p->have_nt, [&](int w, int64_t c0, int cnt) -> int {
     const int k = w & 1;
     if (w >= 2) {  // the slab of window w - 2 must have been drained before it is overwritten
@@ -1819,6 +1890,7 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
   if (rc) return rc;
   for (int w = std::max(0, p->nwin - 2); w < p->nwin; ++w)
     if ((rc = drain(w))) return rc;
+  p->res_order = p->eval_order;
   return check_status(p, u != nullptr);
 }
 
@@ -1840,7 +1912,8 @@ static int evaluate_queued(rtd_plan* p, int32_t ntau, const double* tau, int32_t
   int rc = rtd_plan_set_eval_points(p, ntau, tau, nphi, phi);
   if (rc) return rc;
   const bool skip_nt = (antiderivative & 2) != 0;
-  RtdEval e = make_eval(p, (antiderivative & 1) ? -1 : (antiderivative & 4) ? 1 : 0, want_u);
+  const int order = (antiderivative & 1) ? -1 : (antiderivative & 4) ? 1 : 0;
+  RtdEval e = make_eval(p, order, want_u);
   // one window, or a retained plan (rtd_plan_create_retained): what the evaluators need of the solve is resident for every
   // column, only the evaluation kernels run.  Several windows without retention: they are solved again, window by window,
   // with the evaluation behind each (the throughput form rtd_plan_run is the intended entry point for such batches).
@@ -1848,6 +1921,7 @@ static int evaluate_queued(rtd_plan* p, int32_t ntau, const double* tau, int32_t
   rc = launch_windows(p, solve_again, &e, p->have_nt && !skip_nt, [](int, int64_t, int) { return 0; }, false);
   if (rc) return rc;
   if (p->pipelined && !solve_again) p->fork_needed = true;  // the next solve's eigen stream must not overwrite what this pass still reads
+  p->res_order = order;
   return 0;
 }
 
@@ -1927,6 +2001,62 @@ int rtd_plan_evaluate_band(rtd_plan* p, int32_t ntau, const double* tau, int32_t
   int rc = evaluate_queued(p, ntau, tau, nphi, phi, flags, u != nullptr);
   if (rc) return rc;
   return drained(p, band_fetch_queued(p, u, u0, flux_up, fdn, fdir));
+}
+
+// rtd_actinic_kernel over all columns into ev_act, on the plan's stream: everything it reads is held for all columns
+static int actinic_queued(rtd_plan* p) {
+  HIP_TRY(hipSetDevice(p->device));
+  const int64_t CT = (int64_t)p->d.C * p->ev_ntau;
+  int rc = grow(p, &p->ev_act, &p->cap_act, 3 * CT);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(rtd_actinic_kernel, dim3((unsigned)((CT + 255) / 256)), dim3(256), 0, p->stream, p->d, (const double*)p->ev_tau,
+                     (const double*)p->ev_u0, (int)p->ev_ntau, (int)p->res_order, p->ev_act);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_actinic_kernel: ") + hipGetErrorString(e));
+  return 0;
+}
+
+static int actinic_fetch_queued(rtd_plan* p, double* up, double* dn, double* dir) {
+  int rc = actinic_queued(p);
+  if (rc) return rc;
+  const int64_t CT = (int64_t)p->d.C * p->ev_ntau;
+  double* outs[3] = {up, dn, dir};
+  for (int f = 0; f < 3; ++f)
+    if (outs[f]) HIP_TRY(hipMemcpyAsync(outs[f], p->ev_act + f * CT, (size_t)CT * 8, hipMemcpyDeviceToHost, p->stream));
+  return check_status(p, false);  // (u0 comes from Fourier mode 0 alone)
+}
+
+static int band_actinic_fetch_queued(rtd_plan* p, double* up, double* dn, double* dir) {
+  int rc = actinic_queued(p);
+  if (rc) return rc;
+  const int64_t G = p->band_G, K = p->band_K, P = p->d.C / G, nt = p->ev_ntau, CT = p->d.C * nt;
+  if ((rc = grow(p, &p->rb_act, &p->cap_rb_act, 3 * P * K * nt))) return rc;
+  double* outs[3] = {up, dn, dir};
+  for (int f = 0; f < 3; ++f) {
+    if (!outs[f]) continue;
+    double* out = p->rb_act + f * P * K * nt;
+    hipLaunchKernelGGL(rtd_band_reduce_kernel, dim3((unsigned)((P * nt + 255) / 256)), dim3(256), 0, p->stream,
+                       (const double*)(p->ev_act + f * CT), (const double*)p->band_w, (const int*)p->d.col_status, 0xFF, (long)P, (int)G,
+                       (int)K, (long)nt, out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(outs[f], out, (size_t)(P * K * nt) * 8, hipMemcpyDeviceToHost, p->stream);
+    if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("fetch_band_actinic: ") + hipGetErrorString(e));
+  }
+  return check_status(p, false);
+}
+
+int rtd_plan_fetch_actinic(rtd_plan* p, double* act_up, double* act_down_diffuse, double* act_down_direct) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
+  return drained(p, actinic_fetch_queued(p, act_up, act_down_diffuse, act_down_direct));
+}
+
+int rtd_plan_fetch_band_actinic(rtd_plan* p, double* act_up, double* act_down_diffuse, double* act_down_direct) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede fetch_band_actinic");
+  if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
+  return drained(p, band_actinic_fetch_queued(p, act_up, act_down_diffuse, act_down_direct));
 }
 
 int rtd_plan_set_nt(rtd_plan* p, int32_t nleg_all, const double* weighted_leg_all, const double* f_arr,
@@ -2416,6 +2546,7 @@ int rtd_plan_solve_layers(rtd_plan* p, int32_t first, int32_t count) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   p->solved = false;
+  p->res_order = rtd_plan::RES_NONE;
   return 0;
 }
 

@@ -241,7 +241,8 @@ class Plan:
 
     def evaluate_band(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
         """``evaluate`` without copying the unreduced fields out: tau [C, ntau] (the t-th point of each of a profile's columns must
-        be the same physical level), phi [nphi] or None -> the dict of ``fetch_band`` (include/rtd.h: rtd_plan_evaluate_band)."""
+        be the same physical level), phi [nphi] or None -> the dict of ``fetch_band`` (include/rtd.h: rtd_plan_evaluate_band);
+        "act" in `want` adds the reduced actinic fluxes of ``fetch_band_actinic``."""
         if antiderivative and derivative:
             raise ValueError("antiderivative and derivative exclude each other.")
         tau = _f64(np.atleast_2d(tau))
@@ -254,6 +255,49 @@ class Plan:
         self._checked_band(self._lib.rtd_plan_evaluate_band(
             self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi), int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0),
             *[_lib.dptr(out[k]) for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")]))
+        if "act" in want:
+            out.update(self.fetch_band_actinic())
+        return out
+
+    _ACT = ("flux_act_up", "flux_act_down_diffuse", "flux_act_down_direct")
+
+    def _resident_ntau(self):
+        """Points per column of the results the plan holds now, as the plan itself reports it (include/rtd.h:
+        rtd_plan_result_dev_ptrs, flux_bytes = 3 C ntau 8).  The host arrays of the actinic fetches are sized from this and from
+        nothing this object remembers: evaluate() moves the plan's points without a fetch of the stored ones in mind."""
+        fb = C.c_int64()
+        _lib.check(self._lib.rtd_plan_result_dev_ptrs(self._h, None, None, None, C.byref(fb)))
+        return int(fb.value // (24 * self.C))
+
+    def fetch_actinic(self, out=None):
+        """Actinic fluxes (4 pi x the mean intensity) of the results the plan holds -- after run(), run_fetch(), evaluate() or
+        evaluate_band(), whatever their `want`, at the points and in the order (value, antiderivative, derivative) of the latest
+        of them -- formed on the device from the resident u0 (include/rtd.h: rtd_plan_fetch_actinic) -> dict(flux_act_up,
+        flux_act_down_diffuse, flux_act_down_direct [C, ntau]); diffuse + direct is the physical downward actinic flux.  `out`:
+        dict whose arrays of those names are filled in place (C-contiguous float64 [C, ntau], anything else is a ValueError);
+        the others are allocated."""
+        shape = (self.C, self._resident_ntau())
+        given = out or {}
+        out = {}
+        for k in self._ACT:
+            a = given.get(k)
+            if a is None:
+                a = np.empty(shape)
+            elif not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable and a.shape == shape):
+                raise ValueError(f"out[{k!r}] must be a writeable C-contiguous float64 array of the shape {shape}.")
+            out[k] = a
+        self._checked(self._lib.rtd_plan_fetch_actinic(self._h, *[_lib.dptr(out[k]) for k in self._ACT]), out)
+        return out
+
+    def fetch_band_actinic(self):
+        """``fetch_actinic`` summed over the spectral points with every weight set on the device (include/rtd.h:
+        rtd_plan_fetch_band_actinic) -> the same keys, [P, K, ntau].  With weights = cross section x quantum yield x k-weight the sum
+        of the three is the photolysis rate per level."""
+        if getattr(self, "_band", None) is None:
+            raise ValueError("set_band_weights must precede fetch_band_actinic.")
+        P, K = self._band
+        out = {k: np.empty((P, K, self._resident_ntau())) for k in self._ACT}
+        self._checked_band(self._lib.rtd_plan_fetch_band_actinic(self._h, *[_lib.dptr(out[k]) for k in self._ACT]))
         return out
 
     def close(self):
@@ -335,7 +379,8 @@ class Plan:
 
     def evaluate(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
         """tau [C, ntau]; phi [nphi] or None -> dict of arrays (u [C,Q,ntau,nphi], u0 [C,Q,ntau],
-        flux_up / flux_down_diffuse / flux_down_direct [C,ntau], ulast [C,Q,ntau]).  derivative: every output is its
+        flux_up / flux_down_diffuse / flux_down_direct [C,ntau], ulast [C,Q,ntau]; "act" in `want` adds the actinic fluxes of
+        ``fetch_actinic`` at the same points, in the same order).  derivative: every output is its
         derivative with respect to the unscaled tau (include/rtd.h: bit 2 of rtd_plan_evaluate's flag word; one-sided from above
         at an interface); not together with antiderivative."""
         if antiderivative and derivative:
@@ -357,6 +402,8 @@ class Plan:
                                                   _lib.dptr(u0),
                                                   _lib.dptr(fl[0]), _lib.dptr(fl[1]), _lib.dptr(fl[2]),
                                                   _lib.dptr(ul)), out)
+        if "act" in want:
+            out.update(self.fetch_actinic())
         return out
 
     # ---- throughput form (results stay in HBM until fetch) ----

@@ -190,6 +190,22 @@ class BandSolution:
         """-> [P, K, NQuad, nlev, nphi]"""
         return self._out(self._eval(levels, phi, ("u",))["u"])
 
+    def flux_act_up(self, levels=None):
+        """Upward actinic flux of the band -> [P, K, nlev]"""
+        return self._out(self._eval(levels, None, ("act",))["flux_act_up"])
+
+    def flux_act_down(self, levels=None):
+        """Downward actinic flux of the band -> (diffuse [P, K, nlev], direct [P, K, nlev]); the delta-M reclassification term is
+        applied per column, before the sum over the spectral points (``BatchSolution.flux_act_down``)."""
+        r = self._eval(levels, None, ("act",))
+        return self._out(r["flux_act_down_diffuse"]), self._out(r["flux_act_down_direct"])
+
+    def actinic_flux(self, levels=None):
+        """Total actinic flux up + down diffuse + down direct -> [P, K, nlev].  With weights[k][g] = cross section x quantum yield x
+        the point's k-weight this is the photolysis rate per level."""
+        r = self._eval(levels, None, ("act",))
+        return self._out(r["flux_act_up"] + r["flux_act_down_diffuse"] + r["flux_act_down_direct"])
+
     def net_flux_convergence(self):
         """-> [P, K, L]: F_net[l] - F_net[l + 1], F_net = down_diffuse + down_direct - up: the layers' absorbed power (host
         arithmetic on the reduced level fluxes)."""
@@ -231,13 +247,14 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
 
 def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, levels=None, phi=None,
                         chunk_columns=0, NLeg=None, NFourier=None, delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None,
-                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise"):
+                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False):
     """Throughput form of ``pydisort_band`` (as ``solve_columns_streamed`` is of ``pydisort_batch``): ONE plan holds the inputs
     and the results of all P G columns, the intermediates of the solve live for `chunk_columns` columns at a time, the results at
     `levels` (None: all L + 1) and `phi` are reduced on the device and only the P band results travel to the host -- 1 / G of what
     ``Plan.run_fetch`` moves, so no window-overlapped copy is needed.
     Returns dict(u [P, K, NQuad, nlev, nphi] (absent when only_flux), u0 [P, K, NQuad, nlev], flux_up, flux_down_diffuse,
-    flux_down_direct [P, K, nlev], tau_arr [P, G, L]); the K axis is dropped when ``weights`` was [G]."""
+    flux_down_direct [P, K, nlev], tau_arr [P, G, L]); the K axis is dropped when ``weights`` was [G].  actinic=True adds
+    flux_act_up, flux_act_down_diffuse, flux_act_down_direct [P, K, nlev] (``Plan.fetch_band_actinic``)."""
     if chunk_columns <= 0:  # (as solve_columns_streamed: windows of ~8 192 (column, mode) chains)
         modes = 1 if only_flux else int(NFourier or NLeg or NQuad)
         chunk_columns = max(64, 8192 // max(modes, 1))
@@ -251,6 +268,8 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
         plan.set_eval_points(level_tau(plan.prep["tau"], levels), phi)
         plan.run()
         out = plan.fetch_band(want=("u0", "flux") if only_flux else ("u", "u0", "flux"))
+        if actinic:
+            out.update(plan.fetch_band_actinic())
     finally:
         plan.close()
     out = {k: sol._out(v) for k, v in out.items() if v is not None}

@@ -128,6 +128,19 @@ class BatchSolution:
         r = self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)
         return r["flux_down_diffuse"], r["flux_down_direct"]
 
+    def flux_act_up(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """Upward actinic flux 2 pi sum_i w_i u0_i, formed on the device -> [C, ntau]"""
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("act",), derivative=deriv)["flux_act_up"]
+
+    def flux_act_down(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """Downward actinic flux -> (diffuse [C, ntau], direct [C, ntau]).  The diffuse part carries the reference's delta-M
+        reclassification term I0 e^(-tau* / mu0) - I0 e^(-tau / mu0) with the caller's I0 (``generate_diff_act_flux_funcs``); the
+        direct part is flux_down_direct / mu0; their sum is the physical downward actinic flux."""
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        r = self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("act",), derivative=deriv)
+        return r["flux_act_down_diffuse"], r["flux_act_down_direct"]
+
 
 def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLeg=None, NFourier=None,
                    b_pos=0, b_neg=0, only_flux=False, f_arr=0, NT_cor=False, bdrf_q=None, bdrf_q0=None,
@@ -275,7 +288,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
 
 
 def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=False, out=None, numeric_errors="raise",
-                           *, tau_order=0):
+                           *, tau_order=0, actinic=False):
     """Throughput form for large column counts: ONE plan holds the inputs and the results of all columns, the
     intermediates of the solve (~8 MB per cfg4 column) live for `chunk_columns` columns at a time (0: ~8 192 (column,
     mode) chains per window) and the device-to-host copies of a window overlap the kernels of the next (``Plan.run_fetch``).
@@ -284,11 +297,16 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
     cfg : dict of ``pydisort_batch`` keyword arguments with a leading column axis (tau_arr, omega_arr, Leg_coeffs_all,
           mu0, I0, phi0, optional f_arr, b_pos, b_neg, s_poly_coeffs, bdrf_q, bdrf_q0, NLeg, NFourier); NQuad scalar.
     tau : [C, ntau] evaluation depths; phi : [nphi].
-    out : optional dict of preallocated C-contiguous float64 result arrays to fill (the same keys and shapes).
+    out : optional dict of preallocated C-contiguous float64 result arrays to fill (the same keys and shapes).  Without `actinic`
+          every key of the result is required.  With actinic=True the contract differs in two places: u0 may be absent (it then
+          stays on the device and is not in the result), and an actinic array that is absent is allocated and ADDED to the
+          caller's dict; one that is present is checked like the others and filled in place.
     numeric_errors : as in ``pydisort_batch`` ("nan": failed columns come back as NaN, the rest of the batch is kept).
     tau_order : 0 the values (default), +1 their derivatives with respect to the unscaled tau (as ``is_derivative_wrt_tau`` of the
           evaluators: one-sided from above at an interface), -1 their tau-antiderivatives (``is_antiderivative_wrt_tau``): a
           batch too large to retain gets them host to host through the same window pipeline (``Plan.set_eval_order``).
+    actinic : True adds flux_act_up, flux_act_down_diffuse, flux_act_down_direct [C, ntau] (``Plan.fetch_actinic``), formed on the
+          device from the resident u0 in the same `tau_order`; u0 itself may then be left out of `out` (it is not copied).
     Returns dict(u [C, NQuad, ntau, nphi] (absent when only_flux), u0, flux_up, flux_down_diffuse, flux_down_direct)."""
     if tau_order not in (-1, 0, 1):
         raise ValueError("tau_order must be -1, 0 or +1.")
@@ -314,14 +332,19 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
         shapes = dict(u0=(C, Q, ntau), flux_up=(C, ntau), flux_down_diffuse=(C, ntau), flux_down_direct=(C, ntau))
         if not only_flux:
             shapes["u"] = (C, Q, ntau, len(phi))
+        act = {k: (C, ntau) for k in Plan._ACT} if actinic else {}
         if out is None:
             out = {k: np.empty(shp) for k, shp in shapes.items()}
         else:
-            for k, shp in shapes.items():
+            for k, shp in list(shapes.items()) + list(act.items()):
                 a = out.get(k)
+                if a is None and actinic and (k == "u0" or k in act):
+                    continue  # (with actinic=True the caller may leave u0 on the device; actinic arrays not given are allocated)
                 if a is None or a.shape != shp or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"]:
                     raise ValueError(f"out[{k!r}] must be a C-contiguous float64 array of shape {shp}.")
         plan.run_fetch(out)
+        if actinic:
+            out.update(plan.fetch_actinic(out))
     finally:
         plan.close()
     return out
