@@ -277,6 +277,26 @@ int rtd_plan_evaluate(rtd_plan* plan, int32_t ntau, const double* tau, int32_t n
  * nleg_all <= 0 switches the corrections off. */
 int rtd_plan_set_nt(rtd_plan* plan, int32_t nleg_all, const double* weighted_leg_all, const double* f_arr,
                     const double* ims_coef, const double* ims_par);
+/* The same four inputs formed ON THE DEVICE, for the plans whose columns arrive unprepared: while nleg_all > 0 is requested (sticky;
+ * 0 withdraws the request), rtd_plan_set_columns_raw, _thermal and _band also form weighted_leg_all, ims_coef and ims_par from the
+ * arrays they stage (arithmetic of csrc/rtd_nt_prep.h), keep f_arr, and switch the corrections on.
+ *   raw columns: nleg_all must equal the nleg_all passed there and exceed nleg; weighted_leg_all is [C][L][nleg_all].
+ *   a band:      nleg_all must equal band->nleg_all (> nleg) and band->delta_m must be set.  The mixture's moments do not depend
+ *                on the spectral point: weighted_leg_all is [P][L][nleg_all], one row per profile shared by its G columns, formed
+ *                by the expression behind rtd_band_mix's moments (the same bits); only the IMS constants are per column.
+ *   otherwise RTD_ERR_ARG from those calls; likewise for a plan without a beam, as rtd_plan_set_nt.
+ * The IMS weights are omega_l tau_arr[l] with the CUMULATIVE tau_arr, the reference's convention (:601-610); I0 in the amplitude
+ * is the plan's rescaled beam.  Each column's sums run over l ascending in one chain per moment (one wavefront per column, lanes
+ * over the moments, no atomics, no cross-lane reduction): the bits depend on the inputs alone.  A column with
+ * sum_l f_l omega_l tau_arr[l] = 0 gets ims_coef = 0, amplitude 0 and scaled_mu0 = mu0 -- its IMS term is exactly 0, where the
+ * formulas (and the host-prepared path) give 0 / 0.
+ * While a request is set the host-prepared rtd_plan_set_columns returns RTD_ERR_STATE.  rtd_plan_set_nt(nleg_all <= 0) still
+ * switches the corrections off (until the next columns).  A plan that never requests allocates and launches nothing for this. */
+int rtd_plan_request_nt(rtd_plan* plan, int32_t nleg_all_or_0);
+/* Diagnostic, in the spirit of rtd_plan_get_tensors: what the plan holds of the four inputs, uploaded or device-formed.  wfull
+ * [rows][L][nleg_all] with *rows = C, or P for a band; f [C][L]; ims_coef [C][nleg_all]; ims_par [C][2].  Any pointer may be NULL.
+ * RTD_ERR_STATE when no corrections are set.  Synchronous. */
+int rtd_plan_get_nt(rtd_plan* plan, double* wfull, double* f, double* ims_coef, double* ims_par, int32_t* rows);
 
 /* Throughput form: evaluation points are uploaded once, results stay in HBM. */
 int rtd_plan_set_eval_points(rtd_plan* plan, int32_t ntau, const double* tau, int32_t nphi, const double* phi);

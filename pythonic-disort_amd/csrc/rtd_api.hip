@@ -18,6 +18,7 @@
 #include "rtd_device.h"
 #include "rtd_dd.h"
 #include "rtd_planck.h"
+#include "rtd_nt_prep.h"
 
 namespace {
 
@@ -339,6 +340,8 @@ struct rtd_plan {
   double *nt_w = nullptr, *nt_f = nullptr, *nt_ic = nullptr, *nt_ip = nullptr, *nt_R = nullptr;
   int64_t cap_nt_w = 0, cap_nt_f = 0, cap_nt_ic = 0, cap_nt_ip = 0, cap_nt_R = 0;
   bool have_nt = false, nt_tables_ready = false;
+  int nt_request = 0;   // rtd_plan_request_nt: nleg_all of the device-formed inputs (0: none); sticky
+  int64_t nt_rows = 0;  // rows of nt_w: C, or the P profiles of a band
   // RCCL communicator (one rank per GPU)
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_size = 0;
@@ -460,7 +463,9 @@ RtdEval window_eval(const rtd_plan* p, const RtdEval& e, int64_t c0) {
 RtdNt window_nt(const rtd_plan* p, int64_t c0) {
   RtdNt w = p->nt;
   const int64_t L = p->d.L;
-  w.wfull += c0 * L * w.nleg_all; w.f += c0 * L; w.ims_coef += c0 * w.nleg_all; w.ims_par += c0 * 2;
+  if (w.group > 1) w.c0 = c0;  // rows shared by a band's spectral points: the kernel forms (c0 + c) / group itself
+  else w.wfull += c0 * L * w.nleg_all;
+  w.f += c0 * L; w.ims_coef += c0 * w.nleg_all; w.ims_par += c0 * 2;
   w.R += c0 * 4 * p->d.NP * L;
   return w;
 }
@@ -714,7 +719,7 @@ extern "C" {
 
 int rtd_comm_destroy(rtd_plan* p);
 
-int rtd_version(void) { return 214; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic
+int rtd_version(void) { return 215; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt
 
 const char* rtd_last_error(void) { return g_err.c_str(); }
 
@@ -1079,6 +1084,8 @@ int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* 
   const RtdDev& d = p->d;
   if (d.Ns > 0 && !s_poly) return fail(RTD_ERR_ARG, "s_poly is required when nscoeffs > 0");
   if (d.NBDRF > 0 && (!bdrf_q || !bdrf_q0)) return fail(RTD_ERR_ARG, "BDRF tables are required when nbdrf > 0");
+  if (p->nt_request > 0)
+    return fail(RTD_ERR_STATE, "rtd_plan_request_nt is set: the Nakajima-Tanaka inputs are formed from raw columns (set_columns_raw / _thermal / _band)");
   HIP_TRY(hipSetDevice(p->device));
   const int64_t C = d.C, L = d.L, M = d.M, P = d.P, N = d.N, NP = d.NP, Ns = d.Ns, NB = d.NBDRF;
   // a plan created without a beam skips the beam terms on the device: refuse inputs that have one
@@ -1300,13 +1307,7 @@ __global__ void rtd_band_moments_kernel(RtdBandDev b) {
   const int l = (int)(cl % b.L);
   const double* dt = b.dspec + (p * b.L + l) * b.S;
   const double* om = b.ospec + (p * b.L + l) * b.S;
-  double sca = 0.0, num = 0.0;
-  for (int s = 0; s < b.S; ++s) {
-    const double t = om[s] * dt[s];
-    sca += t;
-    num += t * b.lspec[(long)s * b.nleg_all + k];
-  }
-  b.leg[idx] = k == 0 ? 1.0 : sca != 0.0 ? num / sca : 0.0;
+  b.leg[idx] = rtd_mix_moment(dt, om, b.lspec, b.S, b.nleg_all, k);  // (rtd_nt_prep.h: shared with the band's full phase function)
 }
 
 void band_mix_launch(const RtdBandDev& b, hipStream_t s) {
@@ -1314,6 +1315,57 @@ void band_mix_launch(const RtdBandDev& b, hipStream_t s) {
   hipLaunchKernelGGL(rtd_band_layers_kernel, dim3((unsigned)((n_cl + 255) / 256)), dim3(256), 0, s, b);
   hipLaunchKernelGGL(rtd_band_tau_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, b);
   hipLaunchKernelGGL(rtd_band_moments_kernel, dim3((unsigned)((n_leg + 255) / 256)), dim3(256), 0, s, b);
+}
+
+// The inputs of the Nakajima-Tanaka corrections from what rtd_plan_set_columns_raw / _thermal / _band stage (rtd_plan_request_nt; the
+// arithmetic is rtd_nt_prep.h), all d.C columns.  Like the band and thermal preparation these kernels live in this translation unit:
+// streaming, no LDS, no barrier, no cross-lane operation, so the stand-in runtime of tests/cpu runs them thread by thread.
+struct RtdNtPrep {
+  int nleg_all, group;            // group: columns per row of the full moments (1: raw columns; G: a band)
+  long rows;                      // d.C / group
+  const double *tau, *omega, *f;  // [C][L]  the RAW tau_arr, omega_arr, f_arr (staged or mixed)
+  double* leg;                    // [rows][L][nleg_all] full moments: uploaded (raw columns, only read) or mixed here (band)
+  int S;                          // > 0: a band -- leg is formed from the species' arrays below
+  const double *dspec, *ospec, *lspec;  // [rows][L][S], [rows][L][S], [S][nleg_all]
+  double *wfull, *ims_coef, *ims_par;   // outputs: [rows][L][nleg_all], [C][nleg_all], [C][2]
+};
+
+// One thread per output element, k fastest: reads and writes are contiguous across the wavefront.
+__global__ void rtd_nt_wfull_kernel(RtdNtPrep q, int L) {  // raw columns: (2k + 1) x the uploaded moment
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= q.rows * L * q.nleg_all) return;
+  const int k = (int)(idx % q.nleg_all);
+  q.wfull[idx] = (2.0 * k + 1.0) * q.leg[idx];
+}
+
+// a band: the mixture's moment (rtd_mix_moment, the expression of rtd_band_moments_kernel) once per PROFILE, kept unweighted for the
+// IMS averages and weighted for the TMS series
+__global__ void rtd_nt_wfull_band_kernel(RtdNtPrep q, int L) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= q.rows * L * q.nleg_all) return;
+  const int k = (int)(idx % q.nleg_all);
+  const long rl = idx / q.nleg_all;  // (row, layer)
+  const double g = rtd_mix_moment(q.dspec + rl * q.S, q.ospec + rl * q.S, q.lspec, q.S, q.nleg_all, k);
+  q.leg[idx] = g;
+  q.wfull[idx] = (2.0 * k + 1.0) * g;
+}
+
+// One wavefront per column, lanes striding over k: at each l the wavefront reads 64 consecutive moments.  No LDS, no barrier, no
+// cross-lane operation, no atomics (rtd_nt_prep.h says what each lane sums).
+__global__ void rtd_nt_ims_kernel(RtdDev d, RtdNtPrep q) {
+  const long c = (long)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+  if (c >= d.C) return;
+  const long L = d.L;
+  rtd_nt_ims_lane(d.L, d.P, q.nleg_all, q.tau + c * L, q.omega + c * L, q.f + c * L, q.leg + (c / q.group) * L * q.nleg_all, d.mu0[c],
+                  d.I0[c], (int)(threadIdx.x & 63), 64, q.ims_coef + c * q.nleg_all, q.ims_par + c * 2);
+}
+
+void nt_prepare_launch(const RtdDev& d, const RtdNtPrep& q, hipStream_t s) {  // behind rtd_launch_prepare: reads d.mu0, d.I0
+  const long n = q.rows * d.L * q.nleg_all;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (q.S > 0) hipLaunchKernelGGL(rtd_nt_wfull_band_kernel, grid, dim3(256), 0, s, q, d.L);
+  else hipLaunchKernelGGL(rtd_nt_wfull_kernel, grid, dim3(256), 0, s, q, d.L);
+  hipLaunchKernelGGL(rtd_nt_ims_kernel, dim3((unsigned)(((long)d.C + 3) / 4)), dim3(256), 0, s, d, q);
 }
 
 // argument check shared by rtd_band_mix and rtd_plan_set_columns_band; returns nullptr when the band is fine
@@ -1477,6 +1529,13 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     nleg_all = d.P;  // the staging block holds the moments the solver uses
   }
   if (nleg_all < d.P) return fail(RTD_ERR_ARG, "nleg_all must be >= nleg");
+  const int64_t nt_all = p->nt_request;  // > 0: the Nakajima-Tanaka inputs are formed here too (rtd_plan_request_nt)
+  if (nt_all > 0) {
+    if (!d.beam) return fail(RTD_ERR_ARG, "NT corrections need a beam source");
+    if (band ? (nt_all != band->nleg_all || !band->delta_m) : nt_all != nleg_all)
+      return fail(RTD_ERR_ARG, "request_nt: nleg_all differs from that of the columns (a band also needs delta_m)");
+    if (nt_all <= d.P) return fail(RTD_ERR_ARG, "request_nt: nleg_all must be > nleg");
+  }
   if (th) {
     if (d.Ns != 2) return fail(RTD_ERR_ARG, "thermal sources need a plan with nscoeffs = 2");
     if (!th->temper || !th->wvnmlo || !th->wvnmhi) return fail(RTD_ERR_ARG, "thermal: temper, wvnmlo and wvnmhi are required");
@@ -1500,7 +1559,16 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
                                  (th->emissivity ? C * N : 0) + C * (L + 3) + (th_bpos && !b_pos ? n_b : 0) + (th_bneg && !b_neg ? n_b : 0);
   const int64_t bP = band ? band->nprofiles : 0, bG = band ? band->ngpoints : 0, bS = band ? band->nspecies : 0;
   const int64_t n_abs = bP * bG * L, n_spec = bP * L * bS, n_lspec = band ? bS * band->nleg_all : 0, n_band = n_abs + 2 * n_spec + n_lspec;
-  const int64_t total = 3 * n_cl + n_leg + 3 * C + (b_pos ? n_b : 0) + (b_neg ? n_b : 0) + n_sp + n_th + n_band;
+  const int64_t nt_rows = band ? bP : C, n_mix = (nt_all > 0 && band) ? bP * L * nt_all : 0;  // a band's unweighted full moments
+  const int64_t total = 3 * n_cl + n_leg + 3 * C + (b_pos ? n_b : 0) + (b_neg ? n_b : 0) + n_sp + n_th + n_band + n_mix;
+  if (nt_all > 0) {  // the plan's own buffers, sized as rtd_plan_set_nt sizes them (wfull: one row per profile of a band)
+    int rc;
+    p->have_nt = false;  // (a buffer may move: on again below, once the new inputs are in place)
+    if ((rc = grow(p, &p->nt_w, &p->cap_nt_w, nt_rows * L * nt_all)) || (rc = grow(p, &p->nt_f, &p->cap_nt_f, C * L)) ||
+        (rc = grow(p, &p->nt_ic, &p->cap_nt_ic, C * nt_all)) || (rc = grow(p, &p->nt_ip, &p->cap_nt_ip, C * 2)) ||
+        (rc = grow(p, &p->nt_R, &p->cap_nt_R, C * 4 * NP * L)))
+      return rc;
+  }
   // staging block from the process-wide pool (a raw hipMalloc / hipFree pair synchronises the whole device per call)
   void* raw_v = nullptr;
   size_t raw_got = 0;
@@ -1580,6 +1648,17 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     rtd_launch_prepare(d, r, s);
     e = hipGetLastError();
   }
+  if (e == hipSuccess && nt_all > 0) {  // behind the preparation (reads the plan's mu0 and rescaled I0), before the block goes back
+    RtdNtPrep np{};
+    np.nleg_all = (int)nt_all; np.group = band ? (int)bG : 1; np.rows = nt_rows;
+    np.tau = r.tau; np.omega = r.omega; np.f = r.f;
+    np.leg = band ? q : const_cast<double*>(r.leg);
+    if (band) { np.S = (int)bS; np.dspec = bd.dspec; np.ospec = bd.ospec; np.lspec = bd.lspec; }
+    np.wfull = p->nt_w; np.ims_coef = p->nt_ic; np.ims_par = p->nt_ip;
+    nt_prepare_launch(d, np, s);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(p->nt_f, r.f, (size_t)n_cl * 8, hipMemcpyDeviceToDevice, s);
+  }
   if (band) {  // the host never recomputes tau: the interface detection of rtd_plan_set_eval_points compares the device's bits
     p->h_tau.resize((size_t)n_cl);
     if (e == hipSuccess) e = hipMemcpyAsync(p->h_tau.data(), r.tau, (size_t)n_cl * 8, hipMemcpyDeviceToHost, s);
@@ -1599,6 +1678,12 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   p->fork_needed = true;
   p->tables_valid = false;
   p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read taus0, scale and mu0 of the batch)
+  if (nt_all > 0) {
+    p->nt.nleg_all = (int)nt_all; p->nt.group = band ? (int)bG : 1; p->nt.c0 = 0;
+    p->nt.wfull = p->nt_w; p->nt.f = p->nt_f; p->nt.ims_coef = p->nt_ic; p->nt.ims_par = p->nt_ip; p->nt.R = p->nt_R;
+    p->nt_rows = nt_rows;
+    p->have_nt = true;
+  }
   p->solved = false;
   p->res_order = rtd_plan::RES_NONE;
   return 0;
@@ -2081,10 +2166,32 @@ int rtd_plan_set_nt(rtd_plan* p, int32_t nleg_all, const double* weighted_leg_al
   HIP_TRY(hipMemcpyAsync(p->nt_ic, ims_coef, (size_t)(C * nleg_all) * 8, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(p->nt_ip, ims_par, (size_t)(C * 2) * 8, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
-  p->nt.nleg_all = nleg_all;
+  p->nt.nleg_all = nleg_all; p->nt.group = 1; p->nt.c0 = 0;
+  p->nt_rows = C;
   p->nt.wfull = p->nt_w; p->nt.f = p->nt_f; p->nt.ims_coef = p->nt_ic; p->nt.ims_par = p->nt_ip; p->nt.R = p->nt_R;
   p->have_nt = true;
   p->nt_tables_ready = false;
+  return 0;
+}
+
+int rtd_plan_request_nt(rtd_plan* p, int32_t nleg_all) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  p->nt_request = nleg_all > 0 ? nleg_all : 0;
+  return 0;
+}
+
+int rtd_plan_get_nt(rtd_plan* p, double* wfull, double* f, double* ims_coef, double* ims_par, int32_t* rows) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (!p->have_nt) return fail(RTD_ERR_STATE, "get_nt: no Nakajima-Tanaka inputs are set");
+  HIP_TRY(hipSetDevice(p->device));
+  const int64_t C = p->d.C, L = p->d.L, na = p->nt.nleg_all;
+  hipStream_t s = p->stream;
+  if (wfull) HIP_TRY(hipMemcpyAsync(wfull, p->nt_w, (size_t)(p->nt_rows * L * na) * 8, hipMemcpyDeviceToHost, s));
+  if (f) HIP_TRY(hipMemcpyAsync(f, p->nt_f, (size_t)(C * L) * 8, hipMemcpyDeviceToHost, s));
+  if (ims_coef) HIP_TRY(hipMemcpyAsync(ims_coef, p->nt_ic, (size_t)(C * na) * 8, hipMemcpyDeviceToHost, s));
+  if (ims_par) HIP_TRY(hipMemcpyAsync(ims_par, p->nt_ip, (size_t)(C * 2) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (rows) *rows = (int32_t)p->nt_rows;
   return 0;
 }
 

@@ -96,7 +96,9 @@ struct RtdEval {
 // Nakajima-Tanaka corrections (rtd_nt.hip)
 struct RtdNt {
   int nleg_all;
-  const double* wfull;     // [C][L][nleg_all]  (2l+1) g_l of the full phase function
+  int group;               // columns that share a row of wfull: 1, or the G spectral points of a band's profile
+  long c0;                 // first absolute column of the view when group > 1 (wfull is then NOT offset: windows are not aligned to G)
+  const double* wfull;     // [rows][L][nleg_all]  (2l+1) g_l of the full phase function, row = (c0 + c) / group
   const double* f;         // [C][L]            delta-M truncation fractions
   const double* ims_coef;  // [C][nleg_all]     Legendre series of the IMS correction
   const double* ims_par;   // [C][2]            scaled mu0, amplitude

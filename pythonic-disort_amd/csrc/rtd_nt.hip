@@ -6,6 +6,9 @@
 // single-scattering sums contributed by the layers below (up-streams) / above (down-streams) of each layer;
 // rtd_nt_apply_kernel adds rescale * (TMS + IMS) to u at every requested (tau, phi) -- or their tau-antiderivatives, or
 // their tau-derivatives (ev.deriv: the factors the antiderivative divides by multiply; the value tables R serve).
+// The corrections' own inputs (:601-611) are uploaded (rtd_plan_set_nt) or, for plans whose columns arrive unprepared, formed by the
+// preparation kernels of rtd_api.hip (rtd_plan_request_nt; arithmetic rtd_nt_prep.h): the weighted full phase function of a band is
+// then held once per profile, and RtdNt.group columns read one row of it here.
 #include "rtd_device.h"
 
 namespace {
@@ -64,7 +67,7 @@ __global__ void rtd_nt_apply_kernel(RtdDev d, RtdNt nt, RtdEval ev) {
   const double I0_4pi = d.I0[c] / (4.0 * M_PI);
   constexpr bool dv = DV;
   const bool ad = !DV && ev.antider != 0;
-  const double* wfull = nt.wfull + ((long)c * L + l) * nt.nleg_all;
+  const double* wfull = nt.wfull + (((nt.c0 + c) / nt.group) * L + l) * nt.nleg_all;  // (group 1: c0 = 0, the view's own rows)
   const double* wtrun = d.wleg + ((long)c * L + l) * d.P;
   const double* ims = nt.ims_coef + (long)c * nt.nleg_all;
   const double smu0 = nt.ims_par[c * 2 + 0], amp = nt.ims_par[c * 2 + 1];

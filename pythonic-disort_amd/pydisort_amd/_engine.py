@@ -31,6 +31,8 @@ class Plan:
         self._h = h
         mu, w = _f64(prep["mu"]), _f64(prep["W"])
         _lib.check(lib.rtd_plan_set_quadrature(h, _lib.dptr(mu), _lib.dptr(w)))
+        if prep.get("nt"):
+            self.request_nt(prep["nt"])
         if prep.get("band") is not None:
             self.set_columns_band(prep["band"], prep["cols"], prep.get("thermal"))
         elif prep.get("raw") is not None and prep.get("thermal") is not None:
@@ -135,6 +137,8 @@ class Plan:
                 *[_lib.dptr(a[k]) for k in ("f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")], C.byref(th)))
         # what later checks (set_columns, the closures' tau range, beam terms) compare against follows the new batch
         self.prep = dict(p, tau=a["tau_arr"], mu0=a["mu0"], phi0=a["phi0"], raw=raw, thermal=_thermal, band=None)
+        if getattr(self, "_nt_request", 0):
+            self._nt_nleg_all = self._nt_request
         self.solved = False
 
     def set_columns_band(self, band, cols, thermal=None):
@@ -196,6 +200,8 @@ class Plan:
         _lib.check(self._lib.rtd_plan_set_columns_band(
             self._h, C.byref(bs), *[_lib.dptr(a[k]) for k in ("mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")], th, _lib.dptr(tau)))
         self.prep = dict(p, tau=tau, mu0=a["mu0"], phi0=a["phi0"], band=band, cols=cols, thermal=thermal, raw=None)
+        if getattr(self, "_nt_request", 0):
+            self._nt_nleg_all = self._nt_request
         self.solved = False
         return tau
 
@@ -332,9 +338,28 @@ class Plan:
         """Enable device-side Nakajima-Tanaka corrections of `u` (arrays with a leading column axis)."""
         a = [_f64(v) for v in (weighted_leg_all, f_arr, ims_coef, ims_par)]
         _lib.check(self._lib.rtd_plan_set_nt(self._h, a[0].shape[-1], *[_lib.dptr(v) for v in a]))
+        self._nt_nleg_all = a[0].shape[-1]
 
     def clear_nt(self):
         _lib.check(self._lib.rtd_plan_set_nt(self._h, 0, None, None, None, None))
+
+    def request_nt(self, nleg_all):
+        """While nleg_all > 0 is requested, ``set_columns_raw`` / ``_thermal`` / ``_band`` also form the inputs of the
+        Nakajima-Tanaka corrections on the device and switch them on (include/rtd.h: rtd_plan_request_nt); nleg_all is the number
+        of moments of the raw batch, or of the band's species.  0 withdraws the request."""
+        _lib.check(self._lib.rtd_plan_request_nt(self._h, int(nleg_all)))
+        self._nt_request = max(int(nleg_all), 0)
+
+    def get_nt(self):
+        """What the plan holds of the corrections' inputs, uploaded or device-formed (include/rtd.h: rtd_plan_get_nt) ->
+        dict(wfull [rows, L, nleg_all] with rows = C, or P for a band; f [C, L]; ims_coef [C, nleg_all]; ims_par [C, 2])."""
+        rows = C.c_int32()
+        _lib.check(self._lib.rtd_plan_get_nt(self._h, None, None, None, None, C.byref(rows)))  # (RTD_ERR_STATE without NT)
+        nall = self._nt_nleg_all  # (the call does not report it: that of the last upload, or of the request the columns met)
+        out = dict(wfull=np.empty((rows.value, self.L, nall)), f=np.empty((self.C, self.L)), ims_coef=np.empty((self.C, nall)),
+                   ims_par=np.empty((self.C, 2)))
+        _lib.check(self._lib.rtd_plan_get_nt(self._h, *[_lib.dptr(out[k]) for k in ("wfull", "f", "ims_coef", "ims_par")], None))
+        return out
 
     def solve(self):
         _lib.check(self._lib.rtd_plan_solve(self._h))

@@ -77,6 +77,8 @@ SIGNATURES = {
     "rtd_solve_tensors": (C.c_int, [C.POINTER(rtd_dims), C.c_int32, C.POINTER(rtd_inputs), C.c_int32] + [_dp] * 5),
     "rtd_plan_evaluate": (C.c_int, [_vp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32] + [_dp] * 6),
     "rtd_plan_set_nt": (C.c_int, [_vp, C.c_int32, _dp, _dp, _dp, _dp]),
+    "rtd_plan_request_nt": (C.c_int, [_vp, C.c_int32]),
+    "rtd_plan_get_nt": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "rtd_plan_set_eval_points": (C.c_int, [_vp, C.c_int32, _dp, C.c_int32, _dp]),
     "rtd_plan_set_eval_order": (C.c_int, [_vp, C.c_int32]),
     "rtd_plan_run": (C.c_int, [_vp]),

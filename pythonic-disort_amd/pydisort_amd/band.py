@@ -10,7 +10,7 @@ import numpy as np
 
 from ._engine import Plan
 from ._prepare import double_gauss
-from .batch import BatchSolution, _retention, _thermal_inputs
+from .batch import BatchSolution, _nt_checks, _retention, _thermal_inputs
 
 
 def level_tau(tau_arr, levels=None):
@@ -215,7 +215,7 @@ class BandSolution:
 
 def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=None, NFourier=None,
                   delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None, bdrf_q0=None, thermal=None, device=0,
-                  work_columns=0, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False):
+                  work_columns=0, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False, NT_cor=False):
     """P profiles x G spectral points of a band in one call.
 
     dtau_abs [P, G, L]: absorption optical thickness of each layer at each spectral point; dtau_spec, omega_spec [P, L, S]:
@@ -228,12 +228,23 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
     weights: [G] or [K, G] -- k-distribution weights, several channels' response functions, photolysis cross sections.
     b_pos / b_neg (scalar, [.], [., N] or [., N, NFourier]), bdrf_q [., NBDRF, N, N], bdrf_q0 [., NBDRF, N] and the arrays of
     ``thermal`` (as in ``pydisort_batch``) are per profile, or per column where they differ by g.
-    Everything else as in ``pydisort_batch``.  Not combined with NT corrections, mode shards or communicators.
+    NT_cor=True adds the Nakajima-Tanaka corrections to ``u`` before the spectral sum, their inputs formed on the device
+    (``Plan.request_nt``): the mixture's full weighted phase function once per PROFILE ([P, L, NLeg_all] -- it does not depend on
+    the spectral point), the IMS constants per column.  Needs delta_M, more moments in Leg_spec than NLeg, I0 > 0 in every column
+    and mu0 away from the quadrature nodes (``ValueError``); not with ``thermal``; ignored with only_flux.
+    Everything else as in ``pydisort_batch``.  Not combined with mode shards or communicators.
     Returns (mu_arr, BandSolution)."""
     prep, w, squeeze = _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg, NFourier, delta_M,
                                     only_flux, b_pos, b_neg, bdrf_q, bdrf_q0, thermal)
     if numeric_errors not in ("raise", "nan"):
         raise ValueError('numeric_errors must be "raise" or "nan".')
+    if NT_cor and not only_flux:
+        if not delta_M:
+            raise ValueError("NT_cor needs delta_M: the corrections restore what the truncation removes.")
+        if thermal is not None:
+            raise ValueError("NT_cor is not combined with thermal in a band.")
+        _nt_checks(prep["cols"]["I0"], prep["cols"]["mu0"], prep["N"], prep["P"], prep["band"]["leg_spec"].shape[1])
+        prep["nt"] = prep["band"]["leg_spec"].shape[1]
     form, budget = _retention(retain, retain_bytes, _defer_solve, prep["C"], prep["N"], prep["M"], prep["L"], device)
     plan = Plan(prep, device=device, work_columns=work_columns, retain_bytes=budget, retain_form=form or 0)
     plan.numeric_errors = numeric_errors
@@ -247,21 +258,22 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
 
 def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, levels=None, phi=None,
                         chunk_columns=0, NLeg=None, NFourier=None, delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None,
-                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False):
+                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False, NT_cor=False):
     """Throughput form of ``pydisort_band`` (as ``solve_columns_streamed`` is of ``pydisort_batch``): ONE plan holds the inputs
     and the results of all P G columns, the intermediates of the solve live for `chunk_columns` columns at a time, the results at
     `levels` (None: all L + 1) and `phi` are reduced on the device and only the P band results travel to the host -- 1 / G of what
     ``Plan.run_fetch`` moves, so no window-overlapped copy is needed.
     Returns dict(u [P, K, NQuad, nlev, nphi] (absent when only_flux), u0 [P, K, NQuad, nlev], flux_up, flux_down_diffuse,
     flux_down_direct [P, K, nlev], tau_arr [P, G, L]); the K axis is dropped when ``weights`` was [G].  actinic=True adds
-    flux_act_up, flux_act_down_diffuse, flux_act_down_direct [P, K, nlev] (``Plan.fetch_band_actinic``)."""
+    flux_act_up, flux_act_down_diffuse, flux_act_down_direct [P, K, nlev] (``Plan.fetch_band_actinic``).  NT_cor as in
+    ``pydisort_band``: u is corrected per column on the device before it is reduced."""
     if chunk_columns <= 0:  # (as solve_columns_streamed: windows of ~8 192 (column, mode) chains)
         modes = 1 if only_flux else int(NFourier or NLeg or NQuad)
         chunk_columns = max(64, 8192 // max(modes, 1))
     _, sol = pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=NLeg, NFourier=NFourier,
                            delta_M=delta_M, only_flux=only_flux, b_pos=b_pos, b_neg=b_neg, bdrf_q=bdrf_q, bdrf_q0=bdrf_q0,
                            thermal=thermal, device=device, work_columns=chunk_columns, numeric_errors=numeric_errors, retain=False,
-                           _defer_solve=True)
+                           _defer_solve=True, NT_cor=NT_cor)
     plan = sol.plan
     try:
         phi = np.array([0.0]) if (only_flux or phi is None) else np.atleast_1d(np.asarray(phi, float))

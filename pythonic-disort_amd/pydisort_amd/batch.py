@@ -59,6 +59,14 @@ def _thermal_inputs(thermal, C, L, N, with_bdrf_samples):
     return out
 
 
+def _nt_checks(I0, mu0, N, NLeg, nleg_all):
+    """What the device-formed Nakajima-Tanaka corrections need of a batch, checked on the small arrays before a plan exists."""
+    if not (np.all(I0 > 0) and NLeg < nleg_all):
+        raise ValueError("NT_cor needs a beam source in every column and NLeg < number of Legendre coefficients.")
+    if np.any(np.abs(double_gauss(N)[0][None, :] - np.asarray(mu0, float).reshape(-1, 1)) < 1e-8):
+        raise ValueError("Some quadrature angles come too close to `mu0`. Perturb `NQuad` or `mu0` to rectify this error.")
+
+
 def _retention(retain, retain_bytes, defer_solve, C, N, NFourier, L, device):
     """``retain`` / ``retain_bytes`` of ``pydisort_batch`` -> (form, budget in bytes) for ``Plan``."""
     form = {"auto": 0, True: 0, "full": 1, "lean": 2}.get(retain if isinstance(retain, (str, bool)) else "auto")
@@ -160,7 +168,9 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
     fewer columns than GPUs); the evaluators then return this shard's partial sums -- the shards add up to the full
     result (u0, fluxes and NT corrections come from shard 0 only; ``Plan.allreduce_results`` sums across RCCL ranks).
     device_prepare=True: the delta-M scaling and the source rescaling of pydisort.py:316-372 run on the device from the raw
-    inputs (``rtd_plan_set_columns_raw``) instead of in NumPy -- for throughput batches; not with NT_cor or mode_shard.
+    inputs (``rtd_plan_set_columns_raw``) instead of in NumPy -- for throughput batches; not with mode_shard.  With NT_cor=True the corrections' inputs are formed on the
+    device as well (``Plan.request_nt``: no [C, L, NLeg_all] host array); a column without truncation (f_arr = 0) then gets the TMS
+    term alone, its IMS term is exactly 0.
     thermal=dict(TEMPER=..., WVNMLO=..., WVNMHI=..., BTEMP=None, TTEMP=None, TEMIS=1.0, emissivity=None): the thermal problem as
     DISORT states it -- level temperatures TEMPER [C, L + 1] or [L + 1], the wavenumber band (cm^-1), the temperatures of the bottom
     and top boundaries and the top's emissivity (scalars or [C]; None: that boundary does not emit).  The device integrates the
@@ -242,9 +252,13 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
         if not 0 < nb <= NFourier:
             raise ValueError("Need 0 < NBDRF <= NFourier.")
         bq, bq0 = np.zeros((C, nb, N, N)), np.zeros((C, nb, N))  # placeholders: the device fills the tables
+    nt_device = 0
     if device_prepare:
-        if NT_cor or mode_shard is not None:
-            raise ValueError("device_prepare cannot be combined with NT_cor or mode_shard.")
+        if mode_shard is not None or (NT_cor and th is not None):
+            raise ValueError("device_prepare cannot be combined with mode_shard, nor thermal with NT_cor.")
+        if NT_cor and not only_flux:  # the corrections' inputs are formed on the device too (Plan.request_nt); checks on the small arrays
+            _nt_checks(I0, mu0, N, NLeg, Leg.shape[2])
+            nt_device = Leg.shape[2]
         bp, bn = bc(b_pos), bc(b_neg)
         raw = dict(tau_arr=tau_arr, omega_arr=omega_arr, leg=Leg, f_arr=f_arr, mu0=mu0, I0=I0, phi0=phi0,
                    b_pos=None if bp is None else np.ascontiguousarray(bp.transpose(0, 2, 1)),
@@ -253,7 +267,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
                    bdrf_q=bq if bq.shape[1] > 0 else None, bdrf_q0=bq0 if bq.shape[1] > 0 else None)
         mu, W = double_gauss(N)
         prep = dict(C=C, L=L, N=N, P=NLeg, M=NFourier, Ns=2 if th is not None else sp.shape[2], NBDRF=bq.shape[1],
-                    beam=bool(np.any(I0 > 0)), mu=mu, W=W, tau=tau_arr, raw=raw, thermal=th)
+                    beam=bool(np.any(I0 > 0)), mu=mu, W=W, tau=tau_arr, raw=raw, thermal=th, nt=nt_device)
     else:
         prep = prepare_columns(tau_arr, omega_arr, NQuad, Leg, mu0, I0, phi0, NLeg, NFourier, bc(b_pos), bc(b_neg),
                                f_arr, sp, bq, bq0)
@@ -277,7 +291,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
         plan.set_bdrf_samples(bdrf_samples[0], bdrf_samples[1] if np.any(I0 > 0) else None)
     if not _defer_solve:
         plan.solve()
-    if NT_cor and not only_flux:
+    if NT_cor and not only_flux and not nt_device:
         if not (np.all(I0 > 0) and np.any(f_arr > 0) and NLeg < Leg.shape[2]):
             raise ValueError("NT_cor needs a beam source in every column, f_arr > 0 and NLeg < number of Legendre coefficients.")
         if np.any(np.abs(prep["mu"][None, :] - mu0[:, None]) < 1e-8):
@@ -296,6 +310,7 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
 
     cfg : dict of ``pydisort_batch`` keyword arguments with a leading column axis (tau_arr, omega_arr, Leg_coeffs_all,
           mu0, I0, phi0, optional f_arr, b_pos, b_neg, s_poly_coeffs, bdrf_q, bdrf_q0, NLeg, NFourier); NQuad scalar.
+          NT_cor=True in cfg adds the Nakajima-Tanaka corrections to u, their inputs formed on the device (ignored with only_flux).
     tau : [C, ntau] evaluation depths; phi : [nphi].
     out : optional dict of preallocated C-contiguous float64 result arrays to fill (the same keys and shapes).  Without `actinic`
           every key of the result is required.  With actinic=True the contract differs in two places: u0 may be absent (it then
