@@ -132,6 +132,23 @@ int rtd_plan_set_columns(rtd_plan* plan, const double* scaled_omega, const doubl
                          const double* b_pos, const double* b_neg, const double* s_poly,
                          const double* bdrf_q, const double* bdrf_q0);
 
+/* Thermal source polynomials about the top of their own layer, on the host (no device, no plan).  s_poly [C][L][Ns] are the
+ * user's s_poly_coeffs -- coefficients in the ABSOLUTE, UNSCALED optical depth -- and tau_arr, omega_arr, f_arr [C][L] as
+ * pydisort()'s arguments; s_local [C][L][Ns] receives, per layer, the coefficients in x = scale_tau (tau - top of the layer),
+ * times (1 - omega) / scale_tau, NOT yet divided by the rescale factor: what rtd_plan_set_columns_raw forms on the device, by the
+ * same routine (csrc/rtd_dd.h: one double-double Taylor shift).  The float64 coefficients in the absolute SCALED depth that
+ * rtd_plan_set_columns takes cannot hold a deep polynomial of degree >= 5 (the substitution alone loses 1e-8 of the source at
+ * degree 9 and optical depth 90); a front end that has the user's polynomials goes this way and through
+ * rtd_plan_set_columns_local, which is rtd_plan_set_columns except that its polynomials ARE in this local form (divided by
+ * rescale) and are uploaded as given. */
+int rtd_source_polynomials_local(int64_t ncolumns, int32_t nlayers, int32_t nscoeffs, const double* tau_arr,
+                                 const double* omega_arr, const double* f_arr, const double* s_poly, double* s_local);
+int rtd_plan_set_columns_local(rtd_plan* plan, const double* scaled_omega, const double* tau,
+                               const double* scaled_tau_with_0, const double* scale_tau, const double* wleg,
+                               const double* mu0, const double* I0, const double* phi0, const double* rescale,
+                               const double* b_pos, const double* b_neg, const double* s_local,
+                               const double* bdrf_q, const double* bdrf_q0);
+
 /* The same batch from RAW inputs: the preparation of pydisort.py:316-372 (delta-M scaling of tau, omega and the moments,
  * the thermal source polynomial in the scaled optical depth, the rescaling of every source by the largest one) runs on
  * the device.  For throughput batches: the host hands over what the user gave, nothing is computed per column on the CPU.

@@ -1075,10 +1075,13 @@ int rtd_plan_set_quadrature(rtd_plan* p, const double* mu_pos, const double* wei
   return 0;
 }
 
-int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* tau, const double* taus0,
-                         const double* scale_tau, const double* wleg, const double* mu0, const double* I0,
-                         const double* phi0, const double* rescale, const double* b_pos, const double* b_neg,
-                         const double* s_poly, const double* bdrf_q, const double* bdrf_q0) {
+namespace {
+// rtd_plan_set_columns (s_local = false: s_poly in the absolute scaled depth) and rtd_plan_set_columns_local (true: already about
+// the top of each layer, as rtd_source_polynomials_local leaves them)
+int set_columns_impl(rtd_plan* p, const double* scaled_omega, const double* tau, const double* taus0,
+                     const double* scale_tau, const double* wleg, const double* mu0, const double* I0,
+                     const double* phi0, const double* rescale, const double* b_pos, const double* b_neg,
+                     const double* s_poly, const double* bdrf_q, const double* bdrf_q0, const bool s_local) {
   if (!p || !scaled_omega || !tau || !taus0 || !scale_tau || !wleg || !mu0 || !I0 || !phi0 || !rescale)
     return fail(RTD_ERR_ARG, "null argument");
   const RtdDev& d = p->d;
@@ -1137,10 +1140,12 @@ int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* 
   // The thermal source polynomials arrive as the reference's scaled_s_poly_coeffs: coefficients in the ABSOLUTE scaled optical
   // depth.  The kernels keep them about the top of their own layer (rtd_dd.h): Taylor shift by taus0[l], in double-double.
   std::vector<double> sloc;
-  if (Ns > 0) {
-    sloc.assign(s_poly, s_poly + C * L * Ns);
-    for (int64_t c = 0; c < C; ++c)
-      for (int64_t l = 0; l < L; ++l) rtd_taylor_shift(sloc.data() + (c * L + l) * Ns, (int)Ns, taus0[c * (L + 1) + l]);
+  if (Ns > 0 && s_local) {
+    UP(d.spoly, s_poly, C * L * Ns);
+  } else if (Ns > 0) {
+    sloc.resize((size_t)(C * L * Ns));
+    for (int64_t cl = 0; cl < C * L; ++cl)
+      rtd_taylor_shift_to(s_poly + cl * Ns, sloc.data() + cl * Ns, (int)Ns, taus0[cl / L * (L + 1) + cl % L]);
     UP(d.spoly, sloc.data(), C * L * Ns);
   }
   // pad the per-stream arrays from N to NP
@@ -1190,6 +1195,38 @@ int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* 
   p->nt_tables_ready = false;  // (the Nakajima-Tanaka tables read taus0, scale and mu0 of the batch)
   p->solved = false;
   p->res_order = rtd_plan::RES_NONE;
+  return 0;
+}
+}  // namespace
+
+int rtd_plan_set_columns(rtd_plan* p, const double* scaled_omega, const double* tau, const double* taus0,
+                         const double* scale_tau, const double* wleg, const double* mu0, const double* I0,
+                         const double* phi0, const double* rescale, const double* b_pos, const double* b_neg,
+                         const double* s_poly, const double* bdrf_q, const double* bdrf_q0) {
+  return set_columns_impl(p, scaled_omega, tau, taus0, scale_tau, wleg, mu0, I0, phi0, rescale, b_pos, b_neg, s_poly, bdrf_q, bdrf_q0,
+                          false);
+}
+
+int rtd_plan_set_columns_local(rtd_plan* p, const double* scaled_omega, const double* tau, const double* taus0,
+                               const double* scale_tau, const double* wleg, const double* mu0, const double* I0,
+                               const double* phi0, const double* rescale, const double* b_pos, const double* b_neg,
+                               const double* s_local, const double* bdrf_q, const double* bdrf_q0) {
+  return set_columns_impl(p, scaled_omega, tau, taus0, scale_tau, wleg, mu0, I0, phi0, rescale, b_pos, b_neg, s_local, bdrf_q, bdrf_q0,
+                          true);
+}
+
+int rtd_source_polynomials_local(int64_t ncolumns, int32_t nlayers, int32_t nscoeffs, const double* tau_arr, const double* omega_arr,
+                                 const double* f_arr, const double* s_poly, double* s_local) {
+  if (ncolumns < 0 || nlayers < 1 || nscoeffs < 1 || !tau_arr || !omega_arr || !f_arr || !s_poly || !s_local)
+    return fail(RTD_ERR_ARG, "rtd_source_polynomials_local: null argument or empty dimension");
+  for (int64_t c = 0; c < ncolumns; ++c) {
+    double top = 0.0;
+    for (int64_t l = 0; l < nlayers; ++l) {
+      const int64_t cl = c * nlayers + l;
+      rtd_source_local(s_poly + cl * nscoeffs, s_local + cl * nscoeffs, nscoeffs, top, 1.0 - omega_arr[cl] * f_arr[cl], omega_arr[cl]);
+      top = tau_arr[cl];
+    }
+  }
   return 0;
 }
 

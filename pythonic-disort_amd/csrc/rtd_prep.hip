@@ -38,20 +38,8 @@ __global__ void rtd_prepare_columns_kernel(RtdDev d, RtdRaw r) {
     omega_s[l] = (1.0 - fl) / sc * om[l];
     tau_o[l] = tau[l];
     if (Ns > 0) {
-      // s(tau) = sum_j a_j tau^j in the layer; the kernels want it about the layer's top in the scaled depth (rtd_dd.h):
-      // tau = top + x / sc  ->  b = Taylor shift of a by `top` (double-double), coefficient i divided by sc^i; then / sc, (1 - omega)
-      const double* a = r.spoly + (c * L + l) * Ns;
-      double* o = sp + (long)l * Ns;
-      for (int i = 0; i < Ns; ++i) o[i] = a[i];
-      rtd_taylor_shift(o, Ns, top);
-      const double rsc = 1.0 / sc;
-      double sci = 1.0;  // sc^-i
-      for (int i = 0; i < Ns; ++i) {
-        o[i] *= sci;
-        sci *= rsc;
-      }
-      const double k = (1.0 - om[l]) * rsc;
-      for (int i = 0; i < Ns; ++i) o[i] *= k;
+      // s(tau) = sum_j a_j tau^j in the layer; the kernels want it about the layer's top in the scaled depth (rtd_dd.h)
+      rtd_source_local(r.spoly + (c * L + l) * Ns, sp + (long)l * Ns, Ns, top, sc, om[l]);
     }
     top = tau[l];
   }

@@ -75,8 +75,12 @@ class Plan:
             raise ValueError("prepared batch has a beam source but the plan was created without one")
         keys = ["omega_s", "tau", "tau_s0", "scale_tau", "wleg", "mu0", "I0", "phi0", "rescale",
                 "b_pos", "b_neg", "s_s", "bdrf_q", "bdrf_q0"]
+        local = prep.get("s_local") is not None  # the thermal polynomials about their layers' tops (_prepare.py)
+        if local:
+            keys[keys.index("s_s")] = "s_local"
         arrs = [_f64(prep[k]) for k in keys]
-        _lib.check(self._lib.rtd_plan_set_columns(self._h, *[_lib.dptr(a) for a in arrs]))
+        setter = self._lib.rtd_plan_set_columns_local if local else self._lib.rtd_plan_set_columns
+        _lib.check(setter(self._h, *[_lib.dptr(a) for a in arrs]))
         self.prep = prep
         self.solved = False
 

@@ -58,6 +58,8 @@ SIGNATURES = {
     "rtd_plan_get_column_status": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "rtd_plan_set_quadrature": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_set_columns": (C.c_int, [_vp] + [_dp] * 14),
+    "rtd_plan_set_columns_local": (C.c_int, [_vp] + [_dp] * 14),
+    "rtd_source_polynomials_local": (C.c_int, [C.c_int64, C.c_int32, C.c_int32] + [_dp] * 5),
     "rtd_plan_set_columns_raw": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 9),
     "rtd_plan_set_columns_thermal": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32] + [_dp] * 8 + [C.POINTER(rtd_thermal)]),
     "rtd_planck_band": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp]),

@@ -9,10 +9,10 @@ int main() {
   int n;
   double t;
   while (std::scanf("%d %lf", &n, &t) == 2) {
-    std::vector<double> c(n);
+    std::vector<double> a(n), c(n);
     for (int i = 0; i < n; ++i)
-      if (std::scanf("%lf", &c[i]) != 1) return 1;
-    rtd_taylor_shift(c.data(), n, t);
+      if (std::scanf("%lf", &a[i]) != 1) return 1;
+    rtd_taylor_shift_to(a.data(), c.data(), n, t);
     for (int i = 0; i < n; ++i) std::printf("%.17g%c", c[i], i + 1 < n ? ' ' : '\n');
   }
   return 0;

@@ -1624,8 +1624,9 @@ def test_device_side_preparation_equals_host_preparation(amd):
             a = getattr(dev, fn)(tau, phi) if fn == "u" else getattr(dev, fn)(tau)
             b = getattr(host, fn)(tau, phi) if fn == "u" else getattr(host, fn)(tau)
             scale = np.max(np.abs(b))
-            # cubic thermal source: the recentred coefficients come out of a different operation order (2e-13)
-            assert np.max(np.abs(a - b)) <= (2e-12 if name == "mixed" else 1e-13) * scale, (name, fn, np.max(np.abs(a - b)) / scale)
+            # the cubic thermal source of "mixed" goes through one routine on both sides (csrc/rtd_dd.h: rtd_source_local); its
+            # coefficients still meet the rescale factor as a division here and as a product with the reciprocal there (1.8e-13)
+            assert np.max(np.abs(a - b)) <= (5e-13 if name == "mixed" else 1e-13) * scale, (name, fn, np.max(np.abs(a - b)) / scale)
         fd_a, fd_b = dev.flux_down(tau), host.flux_down(tau)
         assert np.allclose(fd_a[0], fd_b[0], rtol=1e-12, atol=1e-14) and np.allclose(fd_a[1], fd_b[1], rtol=1e-13)
 

@@ -265,19 +265,32 @@ def test_assemble_shim_has_the_references_signature():
     assert len([f for f in os.listdir(d) if f.endswith(".npz")]) >= 8
 
 
+def _dd_shift(cases):
+    """tests/cpu/dd_shift.cpp (rtd_taylor_shift_to of csrc/rtd_dd.h compiled for the CPU, address and undefined-behaviour sanitizers
+    on) over (n, t, coefficients) cases -> the shifted coefficients of each."""
+    import shutil
+    import subprocess
+    import tempfile
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "dd_shift")
+        subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        os.path.join(ROOT, "tests", "cpu", "dd_shift.cpp"), "-o", exe], check=True)
+        text = "".join(f"{n} {t!r} " + " ".join(repr(float(x)) for x in c) + "\n" for n, t, c in cases)
+        out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(cases)
+    return [[float(x) for x in line.split()] for line in out]
+
+
 def test_double_double_taylor_shift_is_exact_to_the_last_bit():
     """csrc/rtd_dd.h moves the origin of the thermal source polynomials to the top of their layer (one double-double Taylor shift
     on upload instead of a cancelling float64 evaluation at every use, subroutines.py:746-862 / pydisort.py:316-338).  Compiled
     for the CPU here (the header is host + device) and held to exact rational arithmetic: every shifted coefficient is the
     correctly rounded value, also where the terms cancel over ten digits (8ARTS_A's bottom layers: a0 = -3.6e5, a1 tau = +3.6e5)."""
-    import shutil
-    import subprocess
-    import tempfile
     from fractions import Fraction
     from math import comb
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
     rng = np.random.default_rng(3)
     cases = [(2, 21.99325904, [-3.61508536e+05, 1.63496454e+04]), (2, 21.9931618, [-5.36654739e+04, 2.42711395e+03]),
              (1, 5.0, [1.25]), (3, 0.0, [1.0, -2.0, 0.5])]
@@ -289,26 +302,64 @@ def test_double_double_taylor_shift_is_exact_to_the_last_bit():
             c[0] = -sum(c[j] * t**j for j in range(1, n)) * (1.0 + 1e-9 * rng.normal())
         cases.append((n, t, c))
     # round-5 advice: the work array holds 16 double-doubles and a 17th coefficient ran past it (the device-prepare path had no
-    # cap).  16 is the last double-double length; 17 and more -- the reference puts no limit on Nscoeffs -- take the float64 scheme
-    # in place.  Built with the address sanitizer: an overrun of the stack array ends the harness.
+    # cap).  16 is the last length of the Ruffini triangle on the stack; 17 and more -- the reference puts no limit on Nscoeffs --
+    # take one double-double Horner pass per coefficient.  Built with the address sanitizer: an overrun of the stack array ends the
+    # harness.
     for n in (15, 16, 17, 24):
         for _ in range(3):
             cases.append((n, float(rng.uniform(0.0, 1.5)), rng.normal(size=n).tolist()))
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "dd_shift")
-        subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        os.path.join(ROOT, "tests", "cpu", "dd_shift.cpp"), "-o", exe], check=True)
-        text = "".join(f"{n} {t!r} " + " ".join(repr(float(x)) for x in c) + "\n" for n, t, c in cases)
-        out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(out) == len(cases)
-    for (n, t, c), line in zip(cases, out):
-        got = [float(x) for x in line.split()]
+    for (n, t, c), got in zip(cases, _dd_shift(cases)):
         tf, cf = Fraction(t), [Fraction(float(x)) for x in c]
         for i in range(n):
             exact = sum(cf[j] * comb(j, i) * tf ** (j - i) for j in range(i, n))
             want = float(exact)  # correctly rounded
-            if n <= 16:
-                assert got[i] == want or abs(got[i] - want) <= abs(want) * 2.3e-16, (n, t, c, i, got[i], want)
-            else:  # float64 Horner: a backward-stable evaluation, measured against the size of the terms it adds
-                size = float(sum(abs(cf[j]) * comb(j, i) * tf ** (j - i) for j in range(i, n)))
-                assert abs(got[i] - want) <= 4e-15 * size, (n, t, i, got[i], want)
+            assert got[i] == want or abs(got[i] - want) <= abs(want) * 2.3e-16, (n, t, c, i, got[i], want)
+
+
+def test_taylor_shift_of_deep_source_polynomials_is_within_one_ulp_for_every_length():
+    """rtd_taylor_shift_to at n = 2 ... 32 -- 16, 17, 20 and 32 among them -- on the polynomials of tests/thermal_deep_cases.py
+    (e^(0.8 k x)-like per layer, stated in the absolute optical depth, where they cancel by up to eight digits) and shifts up to
+    100, against exact rationals: every output coefficient within 1 ulp of the exact value.  Beyond 16 coefficients the header
+    once dropped to plain float64 Horner (1e-5 of the source at Ns = 20, tau = 90)."""
+    from fractions import Fraction
+    from math import comb
+    import thermal_deep_cases as TD
+    cases = []
+    tau = np.cumsum(np.tile([6.6, 3.3], 10))  # layers of 6 and 3, x 1.1: the last top is 95.7, the bottom 99
+    tops = np.concatenate(([0.0], tau[:-1]))
+    for n in range(2, 33):
+        # The rule of thermal_deep_cases at every length: c_i = r_i (rate x thickness)^i / i!, rate = 0.8 k scale ~ 0.2 per unit of
+        # tau.  The terms C(j, i) |a_j| t^(j - i) the shift adds exceed its result by e^(2 rate t), and two 53-bit words hold a sum of
+        # n such terms to 1 ulp of the result while that factor stays under 2^51 / n ~ 1e14: the rate is capped at 13 / t
+        # (e^26 = 2e11, the factor of the committed Ns = 20 columns at their deepest layer) -- a condition on the inputs, taken
+        # from the format, not from the routine.
+        rng = np.random.default_rng(n)
+        rate = np.minimum(0.8 * 0.45 * 0.55, 13.0 / np.maximum(tops, 1.0))
+        a = rate * np.diff(tau, prepend=0.0)
+        c = np.array([[rng.uniform(0.5, 1.0) * al**i / float(np.prod(np.arange(1, i + 1))) for i in range(n)] for al in a])
+        absolute = TD.absolute_exact(c, tau)
+        for l in (1, 7, 12, 19):
+            cases.append((n, float(tops[l]), [float(v) for v in absolute[l]]))
+    for key in ("16_d16", "32_d19", "6_d13", "128_n19"):  # ... and the committed columns' own
+        kw = TD.case(key)
+        for l in (3, len(kw["tau_arr"]) - 1):
+            cases.append((kw["s_poly_coeffs"].shape[1], float(kw["tau_arr"][l - 1]), kw["s_poly_coeffs"][l].tolist()))
+    assert {16, 17, 20, 32} <= {n for n, _, _ in cases} and max(t for _, t, _ in cases) > 95.0
+    strict = set()
+    for (n, t, c), got in zip(cases, _dd_shift(cases)):
+        exact = TD.local_exact(c, t)
+        tf, cf = Fraction(t), [abs(Fraction(float(x))) for x in c]
+        for i in range(n):
+            want = float(exact[i])
+            ulp = Fraction(float(np.spacing(abs(want))))
+            # Two 53-bit words carry a sum of n terms to 2^-104 of the TERMS per step.  Where the terms C(j, i) |a_j| t^(j - i)
+            # exceed the result by more than 2^49 / n (the high coefficients of a long polynomial: n! / (n - i)! / (rate t)^i on
+            # top of e^(2 rate t)) no two-word arithmetic reaches the last bit, and that floor -- n 2^-102 of the terms, 1e-15 of
+            # what plain float64 Horner loses -- is allowed on top of the ulp.  Below it the bound is 1 ulp, bare.
+            terms = sum(cf[j] * comb(j, i) * tf ** (j - i) for j in range(i, n))
+            floor = terms * n / 2**102
+            if floor <= ulp / 8:
+                floor = 0
+                strict.add(n)
+            assert abs(Fraction(got[i]) - exact[i]) <= ulp + floor, (n, t, i, got[i], want, float(floor / ulp))
+    assert strict == set(range(2, 33))  # every length has coefficients held to the bare ulp

@@ -23,7 +23,11 @@ Fixtures: tests/golden/hp/<family>_<seed>.npz = the evaluation points, u [Q, nta
 for the record, the oracle's distance to it.  Families: random32 / random64 / random (the seeded generators of
 tests/test_gpu_random_parity.py), golden (a reference-captured case of tests/golden/ref by name) and phase (a column of
 tests/phase_cases.py, "<NQuad>_<column>": phase functions beyond Henyey-Greenstein, six columns c0 ... c5 per stream count and the
-six-layer column "deep" at 94 and 126 streams; these fixtures also carry both parts of flux_down).
+six-layer column "deep" at 94 and 126 streams; these fixtures also carry both parts of flux_down) and thermal (a column of
+tests/thermal_deep_cases.py, "<NQuad>_<name>": deep thermal source polynomials.  There the float64 coefficients of the source in the
+absolute scaled depth are NOT a common input -- they cannot hold such a polynomial -- and the truth starts from the user's raw
+s_poly_coeffs in exact arithmetic (thermal_inputs); mode 0 only, with the tau-derivative and the tau-antiderivative of u0 and the
+fluxes, the source loss of the two float64 roads on the same inputs and the cancellation factor R).
 
 Usage (build container; minutes per case on 6 processes):
     python3 tools/hp_truth_case.py random32 9 25          # family, seeds ...
@@ -34,6 +38,7 @@ Usage (build container; minutes per case on 6 processes):
                                                           # with HP_WORKERS=8: the 36 up to 128 streams of the first set ~7 min, the 44
                                                           # of the padded stream counts and the deep column ~7 min, 126_deep alone ~4)
     python3 tools/hp_truth_case.py phase all --skip-existing   # only the cases whose fixture is missing
+    python3 tools/hp_truth_case.py thermal 6_d13 32_d16    # columns of tests/thermal_deep_cases.py; "thermal all": the 93 (~4 min, HP_WORKERS=8)
     python3 tools/hp_truth_case.py --near-conservative    # every random32 / random64 seed with an omega > 1 - 1e-5 layer
 """
 import multiprocessing
@@ -62,7 +67,14 @@ def mpf(x):
 def banded_solve(rows, rhs, kl):
     """Gaussian elimination with partial pivoting on a banded system in mpmath numbers.  rows[i] is a dict
     {column: value} of row i; fill stays inside [i - kl, i + 2 kl] as in LAPACK's dgbsv."""
+    return [x[0] for x in banded_solve_multi(rows, [[v] for v in rhs], kl)]
+
+
+def banded_solve_multi(rows, rhs, kl):
+    """``banded_solve`` for several right-hand sides at once: rhs[i] is the list of row i's right-hand sides (one elimination,
+    the same arithmetic per right-hand side) -> x[i] the list of solutions."""
     n = len(rows)
+    K = len(rhs[0])
     zero = mp.mpf(0)
     for c in range(n):
         piv, best = c, abs(rows[c].get(c, zero))
@@ -83,21 +95,35 @@ def banded_solve(rows, rhs, kl):
             rr = rows[r]
             for k, a in tail:
                 rr[k] = rr.get(k, zero) - f * a
-            rhs[r] -= f * rhs[c]
-    x = [zero] * n
+            rc, rr = rhs[c], rhs[r]
+            rhs[r] = [rr[q] - f * rc[q] for q in range(K)]
+    x = [None] * n
     for c in range(n - 1, -1, -1):
-        s = rhs[c]
+        s = list(rhs[c])
         for k, a in rows[c].items():
             if k > c:
-                s -= a * x[k]
-        x[c] = s / rows[c][c]
+                xk = x[k]
+                for q in range(K):
+                    s[q] -= a * xk[q]
+        x[c] = [v / rows[c][c] for v in s]
     return x
 
 
 def solve_mode(args):
     """u^m at the points (ts_pts: delta-scaled optical depths, l_pts: their layers) -> float64 [Q, npts], BEFORE the
-    rescale factor.  Mirrors oracle.gen_and_part_sols / solve_for_coeffs / Solution._um, in 40 digits."""
+    rescale factor.  Mirrors oracle.gen_and_part_sols / solve_for_coeffs / Solution._um, in 40 digits.
+
+    The thermal family (p["s_loc"], mode 0 only): K columns that differ in their thermal source alone, as K right-hand sides of one
+    elimination.  p["s_loc"][k][l] are the source coefficients of column k about the TOP of layer l in the scaled depth, formed in
+    exact arithmetic from the user's raw polynomials (``thermal_inputs``) -- p["s_s"], the float64 coefficients in the absolute
+    scaled depth, is not read -- and the particular solution is evaluated in the local variable (its construction is translation
+    invariant).  Layers with the same scaled inputs share one decomposition.  -> dict(u [K, 3, Q, npts]: value, d/dtau and the
+    antiderivative in tau as the reference's closures define them (_assemble_intensity_and_fluxes.py:170-260: the rates on the
+    exponentials, the polynomial of the ABSOLUTE scaled depth differentiated or integrated from tau* = 0, each over / times
+    scale_tau), term = the largest single term |G_ij b_q x^q z_j| of the particular solutions at the points, [K])."""
     p, m, ts_pts, l_pts = args
+    s_loc = p.get("s_loc")
+    K = len(s_loc) if s_loc is not None else 1
     mp.mp.dps = 40
     L, N, P = p["L"], p["N"], p["P"]
     Q = 2 * N
@@ -128,8 +154,17 @@ def solve_mode(args):
     Y = [leg(x) for x in mu]
     Y0 = leg(-mu0) if beam else None
     Gs, Ks, Bs, Zs = [], [], [], []
+    seen = {}
     for l in range(L):
         c64 = 0.5 * p["omega_s"][l] * p["wleg"][l, m:]
+        same = seen.setdefault((float(p["omega_s"][l]), np.asarray(p["wleg"][l], float).tobytes()), l)
+        if same != l:  # a layer with these very inputs has been decomposed
+            Gs.append(Gs[same])
+            Ks.append(Ks[same])
+            Bs.append(Bs[same])
+            if iso:
+                Zs.append(Zs[same])
+            continue
         if not np.any(np.abs(c64) > 1e-8):  # the reference's shortcut (:119, :162-168), decided on the float64 inputs
             G = mp.zeros(Q)
             for i in range(N):
@@ -203,6 +238,35 @@ def solve_mode(args):
             poly[j] = acc * Zs[l][j]
         return [sum(Gs[l][i, j] * poly[j] for j in range(Q)) for i in range(Q)]
 
+    bq_cache = {}
+
+    def bq_local(k, l):  # [Q][Ns]: b_q(K_j) z_j of column k's source about the top of layer l
+        if (k, l) not in bq_cache:
+            row = s_loc[k][l]
+            fact = [mp.factorial(q) for q in range(Ns)]
+            bq_cache[k, l] = [[sum(fact[jj] / fact[q] * row[jj] / Ks[l][j] ** (jj - q + 1) for jj in range(q, Ns)) * Zs[l][j]
+                               for q in range(Ns)] for j in range(Q)]
+        return bq_cache[k, l]
+
+    def poly_local(k, l, t, order=0):  # [Q]: sum_q b_q z_j x^q at x = t - ts[l], its d/dtau or its antiderivative from tau* = 0
+        x, sc = t - ts[l], mpf(p["scale_tau"][l])
+        out = []
+        for row in bq_local(k, l):
+            if order == 0:
+                out.append(sum(b * x**q for q, b in enumerate(row)))
+            elif order == 1:
+                out.append(sc * sum(q * b * x ** (q - 1) for q, b in enumerate(row) if q))
+            else:
+                out.append(sum(b * (x ** (q + 1) - (-ts[l]) ** (q + 1)) / (q + 1) for q, b in enumerate(row)) / sc)
+        return out
+
+    def vth_local(l, t):  # [Q][K]
+        cols = []
+        for k in range(K):
+            pl = poly_local(k, l, t)
+            cols.append([sum(Gs[l][i, j] * pl[j] for j in range(Q)) for i in range(Q)])
+        return [[cols[k][i] for k in range(K)] for i in range(Q)]
+
     def expo(l, j, t):  # every exponential referenced to the boundary of its layer where it is <= 1
         kk = Ks[l][j]
         return mp.e ** (kk * (t - (ts[l + 1] if kk > 0 else ts[l])))
@@ -212,30 +276,31 @@ def solve_mode(args):
         R = [[(2 if m == 0 else 1) * mpf(p["bdrf"][m][0][i, j]) * mu[j] * w[j] for j in range(N)] for i in range(N)]
         Xs = [mu0 * mpf(p["I0_4pi"]) * 4 * mpf(p["bdrf"][m][1][i]) for i in range(N)]
     n = Q * L
-    rows, rhs = [dict() for _ in range(n)], [zero] * n
+    rows, rhs = [dict() for _ in range(n)], [None] * n
     r = 0
-    v_top = vth(0, ts[0]) if iso else None
+
+    def vthK(l, t):  # [Q][K]
+        return vth_local(l, t) if s_loc is not None else [[v] for v in vth(l, t)]
+    v_top = vthK(0, ts[0]) if iso else None
     for i in range(N):  # top boundary: downward streams
         for j in range(Q):
             rows[r][j] = Gs[0][N + i, j] * expo(0, j, ts[0])
-        rhs[r] = mpf(p["b_neg"][i, m]) - Bs[0][N + i] * mp.e ** (-ts[0] / mu0)
-        if iso:
-            rhs[r] -= v_top[N + i]
+        v = mpf(p["b_neg"][i, m]) - Bs[0][N + i] * mp.e ** (-ts[0] / mu0)
+        rhs[r] = [v - v_top[N + i][k] for k in range(K)] if iso else [v]
         r += 1
     for l in range(L - 1):
         t = ts[l + 1]
         if iso:
-            va, vb = vth(l, t), vth(l + 1, t)
+            va, vb = vthK(l, t), vthK(l + 1, t)
         for i in range(Q):
             for j in range(Q):
                 rows[r][l * Q + j] = Gs[l][i, j] * expo(l, j, t)
                 rows[r][(l + 1) * Q + j] = -Gs[l + 1][i, j] * expo(l + 1, j, t)
-            rhs[r] = (Bs[l + 1][i] - Bs[l][i]) * mp.e ** (-t / mu0)
-            if iso:
-                rhs[r] += vb[i] - va[i]
+            v = (Bs[l + 1][i] - Bs[l][i]) * mp.e ** (-t / mu0)
+            rhs[r] = [v + (vb[i][k] - va[i][k]) for k in range(K)] if iso else [v]
             r += 1
     tb = ts[L]
-    vb = vth(L - 1, tb) if iso else [zero] * Q
+    vb = vthK(L - 1, tb) if iso else [[zero]] * Q
     att = mp.e ** (-tb / mu0) if beam else zero
     GL, BL = Gs[L - 1], Bs[L - 1]
     for i in range(N):  # bottom boundary: upward streams; surface reflection (:288-293, :232, :246-252)
@@ -244,14 +309,40 @@ def solve_mode(args):
             if has_bdrf:
                 g = g - sum(R[i][q] * GL[N + q, j] for q in range(N))
             rows[r][(L - 1) * Q + j] = g * expo(L - 1, j, tb)
-        v = mpf(p["b_pos"][i, m]) - BL[i] * att - vb[i]
-        if has_bdrf:
-            v += sum(R[i][q] * (BL[N + q] * att + vb[N + q]) for q in range(N))
-            if beam:
-                v += Xs[i] * att
-        rhs[r] = v
+        vs = []
+        for k in range(len(vb[0])):
+            v = mpf(p["b_pos"][i, m]) - BL[i] * att - vb[i][k]
+            if has_bdrf:
+                v += sum(R[i][q] * (BL[N + q] * att + vb[N + q][k]) for q in range(N))
+                if beam:
+                    v += Xs[i] * att
+            vs.append(v)
+        rhs[r] = vs
         r += 1
-    Cc = banded_solve(rows, rhs, 3 * N - 1)
+    CK = banded_solve_multi(rows, rhs, 3 * N - 1)
+    if s_loc is not None:
+        out = np.zeros((K, 3, Q, len(ts_pts)))
+        term = [zero] * K
+        gmax = {}
+        for ti, (t64, l) in enumerate(zip(ts_pts, l_pts)):
+            t, l = mpf(t64), int(l)
+            sc = mpf(p["scale_tau"][l])
+            x = t - ts[l]
+            if id(Gs[l]) not in gmax:
+                gmax[id(Gs[l])] = [max(abs(Gs[l][i, j]) for i in range(Q)) for j in range(Q)]
+            for k in range(K):
+                if iso:
+                    term[k] = max([term[k]] + [gmax[id(Gs[l])][j] * abs(b * x**q) for j, row in enumerate(bq_local(k, l))
+                                               for q, b in enumerate(row)])
+                for oi, order in enumerate((0, 1, -1)):
+                    e = [expo(l, j, t) * CK[l * Q + j][k] * (1 if order == 0 else (sc * Ks[l][j]) ** order) for j in range(Q)]
+                    if iso:
+                        e = [a + b for a, b in zip(e, poly_local(k, l, t, order))]
+                    bt = (mp.e ** (-t / mu0) * (1 if order == 0 else (-sc / mu0) ** order)) if beam else zero
+                    for i in range(Q):
+                        out[k, oi, i, ti] = float(Bs[l][i] * bt + sum(Gs[l][i, j] * e[j] for j in range(Q)))
+        return dict(u=out, term=np.array([float(v) for v in term]))
+    Cc = [v[0] for v in CK]
     out = np.zeros((Q, len(ts_pts)))
     for ti, (t64, l) in enumerate(zip(ts_pts, l_pts)):
         t = mpf(t64)
@@ -417,6 +508,99 @@ def case_phase(key):
     return (kw,) + tuple(phase_cases.points(kw))
 
 
+def thermal_inputs(kw):
+    """(prepared inputs of the hot path WITHOUT the float64 source polynomials' say, the source coefficients about the top of each
+    layer in the scaled depth as 40-digit numbers [L][Ns], divided by the rescale factor): formed from the RAW s_poly_coeffs,
+    tau_arr, omega and the float64 scale_tau in exact rational arithmetic (tests/thermal_deep_cases.py: exact_local_scaled)."""
+    import thermal_deep_cases as TD
+    kw = dict(kw)
+    kw.pop("NT_cor", None)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        p = O.prepare(**kw)
+    if not p["beam"]:
+        p["mu0"] = 1.0
+    exact, _ = TD.exact_local_scaled(kw)
+    res = mpf(p["rescale"])
+    return p, [[mp.mpf(b.numerator) / mp.mpf(b.denominator) / res for b in row] for row in exact]
+
+
+def solve_thermal(job):
+    """Mode 0 of the columns `kws` of ONE atmosphere (they differ in s_poly_coeffs only) at the optical depths tau ->
+    per column dict(u0 [3, Q, ntau]: value, d/dtau, antiderivative; flux_up, flux_down_diffuse [3, ntau]; R)."""
+    kws, tau = job
+    mp.mp.dps = 40
+    prepared = [thermal_inputs(kw) for kw in kws]
+    p = dict(prepared[0][0])
+    Ns = max(len(s[0]) for _, s in prepared)
+    zero = mp.mpf(0)
+    # one rescale factor for the common elimination: every column's source in the units of the first column's factor
+    p["s_loc"] = [[list(row) + [zero] * (Ns - len(row)) for row in
+                   [[b * mpf(q["rescale"]) / mpf(p["rescale"]) for b in r] for r in s]] for q, s in prepared]
+    p["Ns"], p["iso"] = Ns, True
+    _, l_pts, ts_pts = O.Solution._locate(type("S", (), {"p": p})(), tau)
+    sol = solve_mode((p, 0, ts_pts, l_pts))
+    N, wts = p["N"], 2 * np.pi * (p["mu"] * p["W"])
+    out = []
+    for k in range(len(kws)):
+        u0 = p["rescale"] * sol["u"][k]
+        out.append(dict(u0=u0, flux_up=np.einsum("i,oit->ot", wts, u0[:, :N]), flux_down_diffuse=np.einsum("i,oit->ot", wts, u0[:, N:]),
+                        R=p["rescale"] * sol["term"][k] / np.max(np.abs(u0[0]))))
+    return out
+
+
+def _thermal_losses(kw):
+    """Source error, over the layer's largest source value, of the two float64 roads on these inputs: the substitution
+    tau* = scale tau + shift of the reference's front end (then shifted exactly to the layer's top), and the plain-Horner Taylor
+    shift of the raw polynomial."""
+    import thermal_deep_cases as TD
+    from fractions import Fraction
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        p = O.prepare(**kw)
+    exact, width = TD.exact_local_scaled(kw)
+    res = Fraction(float(p["rescale"]))
+    sub = [[b * res for b in TD.local_exact(p["s_s"][l], p["tau_s0"][l])] for l in range(p["L"])]
+    tau = np.atleast_1d(kw["tau_arr"])
+    top = np.concatenate(([0.0], tau[:-1]))
+    a = np.atleast_2d(kw["s_poly_coeffs"])
+    raw_exact = [TD.local_exact(a[l], top[l]) for l in range(p["L"])]
+    horner = [TD.horner_shift(a[l], float(top[l])) for l in range(p["L"])]
+    thick = [Fraction(float(tau[l])) - Fraction(float(top[l])) for l in range(p["L"])]
+    return TD.source_error(sub, exact, width)[0], TD.source_error(horner, raw_exact, thick)[0]
+
+
+def run_thermal(keys):
+    """The columns of tests/thermal_deep_cases.py: the columns of one atmosphere (stream count; delta-M, its twin or the thin one)
+    are the right-hand sides of one elimination; the atmospheres go through one pool, the largest first."""
+    import thermal_deep_cases as TD
+    t0 = time.time()
+    groups = {}
+    for key in keys:
+        q, name = key.split("_")
+        groups.setdefault((int(q), "thin" if name == "thin" else name[0]), []).append(key)
+    order = sorted(groups, key=lambda g: -g[0] ** 3 * TD.layer_count(g[0]))
+    jobs = [([TD.case(k) for k in groups[g]], TD.points(TD.case(groups[g][0]))) for g in order]
+    with multiprocessing.Pool(WORKERS) as pool:
+        sols = pool.map(solve_thermal, jobs, chunksize=1)
+    os.makedirs(OUT, exist_ok=True)
+    for g, (kws, tau), sol in zip(order, jobs, sols):
+        for key, kw, s in zip(groups[g], kws, sol):
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                ref = O.pydisort(**kw)
+            sub, horner = _thermal_losses(kw)
+            res = dict(tau=tau, u0=s["u0"][0], flux_up=s["flux_up"][0], flux_down_diffuse=s["flux_down_diffuse"][0],
+                       flux_down_direct=np.zeros(len(tau)), R=s["R"], loss_substitution=sub, loss_horner=horner,
+                       oracle_u0_scale_rel=np.max(np.abs(ref[3](tau) - s["u0"][0])) / np.max(np.abs(s["u0"][0])))
+            for oi, order_name in ((1, "derivative"), (2, "antiderivative")):
+                for qn in ("u0", "flux_up", "flux_down_diffuse"):
+                    res[f"{order_name}.{qn}"] = s[qn][oi]
+            np.savez_compressed(TD.fixture_path(key), **res)
+            print(f"thermal/{key}: {time.time() - t0:.0f} s; R {float(s['R']):.1e}, loss substitution {sub:.1e} horner {horner:.1e}, "
+                  f"oracle vs truth u0 {float(res['oracle_u0_scale_rel']):.2e}", flush=True)
+
+
 def _record(family, key, kw, tau, phi, u, u0, fup, seconds):
     kwo = dict(kw)
     kwo.pop("NT_cor", None)
@@ -483,11 +667,19 @@ if __name__ == "__main__":
         todo = [t for t in todo if t != ("phase", "all")] + [("phase", k) for k in phase_cases.keys() + [phase_cases.NEGATIVE]]
     if "--skip-existing" in sys.argv:
         todo = [(f, k) for f, k in todo if f == "golden" or not os.path.exists(os.path.join(OUT, f"{f}_{k}.npz"))]
+    if ("thermal", "all") in todo:
+        import thermal_deep_cases
+        todo = [t for t in todo if t != ("thermal", "all")] + [("thermal", k) for k in thermal_deep_cases.keys()]
+        if "--skip-existing" in sys.argv:
+            todo = [(f, k) for f, k in todo if f != "thermal" or not os.path.exists(thermal_deep_cases.fixture_path(k))]
     phase = [k for f, k in todo if f == "phase"]
     if phase:
         run_phase(phase)
+    thermal = [k for f, k in todo if f == "thermal"]
+    if thermal:
+        run_thermal(thermal)
     for family, key in todo:
-        if family == "phase":
+        if family in ("phase", "thermal"):
             continue
         if family == "golden":
             run_golden(key)
