@@ -21,7 +21,8 @@ three parties.  Nakajima-Tanaka corrections are post-processing and are left out
 
 Fixtures: tests/golden/hp/<family>_<seed>.npz = the evaluation points, u [Q, ntau, nphi], u0, flux_up of the truth and,
 for the record, the oracle's distance to it.  Families: random32 / random64 / random (the seeded generators of
-tests/test_gpu_random_parity.py), golden (a reference-captured case of tests/golden/ref by name) and phase (a column of
+tests/test_gpu_random_parity.py), golden (a reference-captured case of tests/golden/ref by name), chain (a column of
+tests/chain_cases.py, "<NQuad>_L<L>[_s<k>]": deep ill-conditioned chains of up to 41 layers; fields as a phase fixture) and phase (a column of
 tests/phase_cases.py, "<NQuad>_<column>": phase functions beyond Henyey-Greenstein, six columns c0 ... c5 per stream count and the
 six-layer column "deep" at 94 and 126 streams; these fixtures also carry both parts of flux_down) and thermal (a column of
 tests/thermal_deep_cases.py, "<NQuad>_<name>": deep thermal source polynomials.  There the float64 coefficients of the source in the
@@ -38,6 +39,11 @@ Usage (build container; minutes per case on 6 processes):
                                                           # with HP_WORKERS=8: the 36 up to 128 streams of the first set ~7 min, the 44
                                                           # of the padded stream counts and the deep column ~7 min, 126_deep alone ~4)
     python3 tools/hp_truth_case.py phase all --skip-existing   # only the cases whose fixture is missing
+    python3 tools/hp_truth_case.py chain 32_L21 64_L25_s3  # columns of tests/chain_cases.py; "chain all": every one of the 33 (~5 min with
+                                                          # HP_WORKERS=8; a mode of 128_L9 is the longest single job, ~2.5 min)
+    python3 tools/hp_truth_case.py chain all --skip-existing
+    python3 tools/hp_truth_case.py fed chain 96_L9_s2 dump.npz   # the 40-digit BC solve and evaluation fed with a device plan's exported
+                                                          # G, K, B (run_fed): separates the eigen stage from the elimination
     python3 tools/hp_truth_case.py thermal 6_d13 32_d16    # columns of tests/thermal_deep_cases.py; "thermal all": the 93 (~4 min, HP_WORKERS=8)
     python3 tools/hp_truth_case.py --near-conservative    # every random32 / random64 seed with an omega > 1 - 1e-5 layer
 """
@@ -155,7 +161,14 @@ def solve_mode(args):
     Y0 = leg(-mu0) if beam else None
     Gs, Ks, Bs, Zs = [], [], [], []
     seen = {}
+    fed = p.get("fed")  # G [M, L, Q, Q], K, B [M, L, Q] of a device plan (Plan.tensors): the eigen stage is then the device's
     for l in range(L):
+        if fed is not None:
+            assert not iso, "fed tensors: beam and boundary sources only"
+            Gs.append(mp.matrix([[mpf(x) for x in row] for row in fed["G"][m][l]]))
+            Ks.append([mpf(x) for x in fed["K"][m][l]])
+            Bs.append([mpf(x) for x in fed["B"][m][l]])
+            continue
         c64 = 0.5 * p["omega_s"][l] * p["wleg"][l, m:]
         same = seen.setdefault((float(p["omega_s"][l]), np.asarray(p["wleg"][l], float).tobytes()), l)
         if same != l:  # a layer with these very inputs has been decomposed
@@ -613,7 +626,7 @@ def _record(family, key, kw, tau, phi, u, u0, fup, seconds):
         res.update(u=u, oracle_u_scale_rel=np.max(np.abs(ou - u)) / np.max(np.abs(u)))
         big = np.abs(u) > 1e-8 * np.max(np.abs(u))
         res["oracle_u_pointwise_rel"] = np.max(np.abs(ou - u)[big] / np.abs(u)[big])
-    if family == "phase":
+    if family in ("phase", "chain"):
         res["flux_down_diffuse"], res["flux_down_direct"] = flux_down_of(kw, tau, u0)
     os.makedirs(OUT, exist_ok=True)
     np.savez_compressed(os.path.join(OUT, f"{family}_{key}.npz"), **res)
@@ -628,20 +641,58 @@ def run(family, key):
     _record(family, key, kw, tau, phi, u, u0, fup, time.time() - t0)
 
 
-def run_phase(keys):
-    """The cases of tests/phase_cases.py: the Fourier modes of ALL of them through one pool, the largest first (a case has three
-    modes only, so case by case the workers would idle)."""
+def case_chain(key):
+    """A column of tests/chain_cases.py, "<NQuad>_L<L>" or "<NQuad>_L<L>_s<k>", at its own points."""
+    import chain_cases
+    kw = chain_cases.case(key)
+    return (kw,) + tuple(chain_cases.points(kw))
+
+
+def run_phase(keys, family="phase"):
+    """The cases of tests/phase_cases.py (or, family "chain", of tests/chain_cases.py): the Fourier modes of ALL of them through one
+    pool, the largest first (a case has three modes only, so case by case the workers would idle)."""
     t0 = time.time()
-    cases = {key: case_phase(key) for key in keys}
+    cases = {key: (case_chain if family == "chain" else case_phase)(key) for key in keys}
     prepared = {key: _mode_jobs(kw, tau) for key, (kw, tau, phi) in cases.items()}
-    order = sorted(keys, key=lambda k: -cases[k][0]["NQuad"])
+    # the cost of a mode: the banded elimination, ~ NQuad^3 per layer
+    order = sorted(keys, key=lambda k: -cases[k][0]["NQuad"] ** 3 * len(cases[k][0]["tau_arr"]))
     flat = [(key, job) for key in order for job in prepared[key][1]]
     with multiprocessing.Pool(WORKERS) as pool:
         ums = pool.map(solve_mode, [job for _, job in flat], chunksize=1)
     for key in order:
         kw, tau, phi = cases[key]
         u, u0, fup = _from_modes(prepared[key][0], [um for (k, _), um in zip(flat, ums) if k == key], phi)
-        _record("phase", key, kw, tau, phi, u, u0, fup, time.time() - t0)
+        _record(family, key, kw, tau, phi, u, u0, fup, time.time() - t0)
+
+
+def run_fed(family, key, dump):
+    """Who owns a distance from the truth: the 40-digit boundary-condition solve and evaluation fed with the tensors G, K, B that a
+    device plan exported (Plan.tensors of the one-column solve, saved with np.savez beside the device's own u, u0, flux_up at the
+    case's points).  fed <-> truth is what the eigen stage's float64 tensors cost, device <-> fed what elimination and evaluation
+    add (10_c0, the deep chains).  Prints both per quantity and the point of the worst pointwise figure."""
+    kw, tau, phi = (case_chain if family == "chain" else case_phase)(key)
+    z = np.load(dump)
+    t0 = time.time()
+    p, jobs = _mode_jobs(kw, tau)
+    p["fed"] = dict(G=z["G"], K=z["K"], B=z["B"])
+    with multiprocessing.Pool(min(WORKERS, p["M"])) as pool:
+        um = pool.map(solve_mode, jobs, chunksize=1)
+    fed = dict(zip(("u", "u0", "flux_up"), _from_modes(p, um, phi)))
+    truth = np.load(os.path.join(OUT, f"{family}_{key}.npz"))
+    np.savez_compressed(os.path.splitext(dump)[0] + "_fed.npz", **fed)
+
+    def dist(a, b):
+        scale = np.max(np.abs(b))
+        big = np.abs(b) > 1e-8 * scale
+        rel = np.where(big, np.abs(a - b) / np.where(big, np.abs(b), 1.0), 0.0)
+        at = np.unravel_index(np.argmax(rel), rel.shape)
+        return (f"{np.max(np.abs(a - b)) / scale:.2e} of the scale, {rel[at]:.2e} pointwise at {tuple(int(i) for i in at)} "
+                f"(|value| {abs(b[at]) / scale:.1e} of the scale, |error| {abs(a[at] - b[at]) / scale:.1e})")
+    print(f"fed {family}/{key}: {time.time() - t0:.0f} s")
+    for k in ("u", "u0", "flux_up"):
+        print(f"  {k}: fed    <-> truth: {dist(fed[k], truth[k])}")
+        print(f"  {k}: device <-> truth: {dist(z[k], truth[k])}")
+        print(f"  {k}: device <-> fed:   {dist(z[k], fed[k])}", flush=True)
 
 
 def near_conservative_seeds():
@@ -655,6 +706,9 @@ def near_conservative_seeds():
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["fed"]:
+        run_fed(*sys.argv[2:5])
+        sys.exit(0)
     if "--near-conservative" in sys.argv:
         todo = near_conservative_seeds()
         if "--list" in sys.argv:
@@ -665,6 +719,9 @@ if __name__ == "__main__":
     if ("phase", "all") in todo:
         import phase_cases
         todo = [t for t in todo if t != ("phase", "all")] + [("phase", k) for k in phase_cases.keys() + [phase_cases.NEGATIVE]]
+    if ("chain", "all") in todo:
+        import chain_cases
+        todo = [t for t in todo if t != ("chain", "all")] + [("chain", k) for k in chain_cases.keys()]
     if "--skip-existing" in sys.argv:
         todo = [(f, k) for f, k in todo if f == "golden" or not os.path.exists(os.path.join(OUT, f"{f}_{k}.npz"))]
     if ("thermal", "all") in todo:
@@ -675,11 +732,14 @@ if __name__ == "__main__":
     phase = [k for f, k in todo if f == "phase"]
     if phase:
         run_phase(phase)
+    chain = [k for f, k in todo if f == "chain"]
+    if chain:
+        run_phase(chain, "chain")
     thermal = [k for f, k in todo if f == "thermal"]
     if thermal:
         run_thermal(thermal)
     for family, key in todo:
-        if family in ("phase", "thermal"):
+        if family in ("phase", "chain", "thermal"):
             continue
         if family == "golden":
             run_golden(key)
