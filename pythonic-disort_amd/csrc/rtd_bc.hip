@@ -68,6 +68,16 @@ namespace {
 #ifndef RTD_GJ_FMAC_DPP
 #define RTD_GJ_FMAC_DPP 1
 #endif
+// RTD_BC_SADDR: the kernel's global loads and stores in the two sweeps, at the turn and in the flush take a wave-uniform base
+// and a 32-bit lane offset (ldg_u / stg_u, rtd_bc_tile_common.h) instead of a per-lane 64-bit pointer.  Addresses only: the
+// order and the number of the memory operations -- what the counted waits rest on -- and every floating-point operation are
+// those of the RTD_BC_SADDR=0 form (tests/test_gpu_bc32_bits.py holds the results to the bit).  (One exception, outside the
+// sweeps' counted waits: the flush's two predicated stores are written that way too, and the compiler then sinks them into ONE
+// store per staged row with a selected per-lane base -- the same lanes and bytes; the flush waits for vmcnt(0) itself.  The
+// window fills keep their per-lane pointers.  HISTORY.md: "Scalar-base addressing in the 32-stream BC kernel".)
+#ifndef RTD_BC_SADDR
+#define RTD_BC_SADDR 1
+#endif
 template <int K, int Q0, int Q1>
 struct FmacRows {  // v[q] -= bcast_K(v[q]) * f for q in [Q0, Q1)
   static __device__ __forceinline__ void run(double (&v)[4], const double f) {
@@ -168,7 +178,7 @@ struct GjPiv {
 
 // Four wavefronts per SIMD: <= 128 registers and <= 10 KB of LDS each, so the kernel prefetches one layer ahead, forms the
 // interface products one after the other (one accumulator set live), takes exp(-k dtau) from memory, saves t^T once and
-// rotates two operand sets in the backward sweep (128 VGPRs, 36 dwords spilled outside the two loops -- profiles/rNN_kernel_resources.json; 9.8 KB).  The kernel
+// rotates two operand sets in the backward sweep (128 VGPRs, 13 dwords spilled outside the two loops with RTD_BC_SADDR, 22 without -- profiles/bc32_diet/kernel_resources*.json; 9.8 KB).  The kernel
 // is bound by the latency of its dependent chains: a three-wavefront form (two layers of prefetch, the products side by
 // side, exp(-k dtau) in the LDS window: 168 VGPRs, 12.7 KB; removed in round 3) took 4.19-4.25 ms per 2 048 cfg4 columns
 // against this form's 4.08-4.11 ms, and padded to 7 / 9 / 12 wavefronts per CU 5.46 / 4.82 / 4.33 ms.
@@ -423,6 +433,16 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     const int ln = min(l + 1, Lm1), l2 = min(l + 2, Lm1);
     v4f64 a2 = a1, y2 = y1, e1r_g = a1;
     double k2c = k1c, e0c_g = 0.0;
+#if RTD_BC_SADDR
+    const LaneOff lo = lane_offsets(lv);
+    {  // one layer ahead: consumed behind this iteration's elimination
+      a1 = load_d_u(Am + (long)ln * NN, lo.lane8);
+      y1 = load_d_u(Ym + (long)ln * NN, lo.lane8);
+      k1c = ldg_u(kk + ln * NP, lo.col8);
+      e0c_g = ldg_u(Ek + l * NP, lo.col8);
+      e1r_g = load_row_u(Ek + ln * NP, lo.kq8);
+    }
+#else
     {  // one layer ahead: consumed behind this iteration's elimination
       a1 = load_d(Am + (long)ln * NN, kq, col);
       y1 = load_d(Ym + (long)ln * NN, kq, col);
@@ -430,6 +450,7 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
       e0c_g = Ek[l * NP + col];
       e1r_g = load_row(Ek + ln * NP, kq);
     }
+#endif
     if (ln >= wb + W) fill(l, false);
     RTD_STAMP();  // 4 l + 1: loop top (register rotation, loads issued)
     const int r0 = l - wb, r1 = ln - wb;
@@ -479,10 +500,22 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     RTD_STAMP();  // 4 l + 2: elimination
     if (l == Lm1) break;
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the loads of this iteration, before the stores go out
+#if RTD_BC_SADDR
+    // (S, rho_b and s lie 4 096 ... 6 528 bytes into the slot, past the 13-bit immediate: the scalar base is taken at S through an
+    //  opaque byte offset, or the compiler folds the constants back into one and builds the address in vector registers after
+    //  all.  The offset, not the pointer: a pointer out of an asm statement is a flat one)
+    long wso = 8 * ((long)l * Ws<NP>::SLOT + Ws<NP>::S);
+    asm("" : "+s"(wso));
+    double* wS = reinterpret_cast<double*>(reinterpret_cast<char*>(wsb) + wso);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) stg_u(wS, block_local(lo.lane8), 512 * q, tb[q]);  // element [4 q + kq][col]
+    if (kq == 0) stg_u(wS, block_local(lo.col8), 8 * (Ws<NP>::SV - Ws<NP>::S), tv);
+#else
     double* ws = wsb + (long)l * Ws<NP>::SLOT;
 #pragma unroll
     for (int q = 0; q < 4; ++q) ws[Ws<NP>::S + (4 * q + kq) * NP + col] = tb[q];
     if (kq == 0) ws[Ws<NP>::SV + col] = tv;
+#endif
     {
       // the same quantities with one accumulator set live at a time (Y_l is scaled in place: it is not used again)
       v4f64 a1s;
@@ -507,7 +540,11 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
         rt = 0.25 * sum_kq(rt);
         rb = 0.25 * sum_kq(rb);
       }
+#if RTD_BC_SADDR
+      if (kq == 0) stg_u(wS, block_local(lo.col8), 8 * (Ws<NP>::RB - Ws<NP>::S), rb);
+#else
       if (kq == 0) ws[Ws<NP>::RB + col] = rb;
+#endif
       const double e0c = e0c_g;
       v4f64 he;
 #pragma unroll
@@ -675,11 +712,20 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     for (int k2 = 0; k2 < nstage; ++k2) {
       const long row = ltop - k2;
       const double v = sOut[k2 * 64 + lane];
+#if RTD_BC_SADDR
+      const unsigned lane8 = (unsigned)lane << 3;
+      if (lane < 32) {
+        if (row < L) stg_u(coef + row * Q, lane8, 0, v);
+      } else if (um) {
+        stg_u(um + row * Q, lane8, -8 * 32, v);  // element lane - 32
+      }
+#else
       if (lane < 32) {
         if (row < L) coef[row * Q + lane] = v;
       } else if (um) {
         um[row * Q + lane - 32] = v;
       }
+#endif
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();
@@ -738,8 +784,22 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
   auto load_set = [&](const int l) {
     int lv = lane;
     asm volatile("" : "+v"(lv));
-    const int kq = lv >> 4, col = lv & 15;
     BwSet s;
+#if RTD_BC_SADDR
+    const LaneOff lo = lane_offsets(lv);
+    s.a = load_d_u(Am + (long)l * NN, lo.lane8);
+    s.y = load_d_u(Ym + (long)l * NN, lo.lane8);
+    long wso = 8 * ((long)l * Ws<NP>::SLOT + Ws<NP>::S);  // (opaque: see the forward loop's stores)
+    asm("" : "+s"(wso));
+    const double* wS = reinterpret_cast<const double*>(reinterpret_cast<const char*>(wsb) + wso);
+    s.h = load_d_u(wS, lo.lane8);
+    s.sl = ldg_u(wS, lo.col8, 8 * (Ws<NP>::SV - Ws<NP>::S));
+    s.rb = ldg_u(wS, lo.col8, 8 * (Ws<NP>::RB - Ws<NP>::S));
+    s.k = ldg_u(kk + l * NP, lo.col8);
+    s.e = 0.0;
+    s.e = ldg_u(Ek + l * NP, lo.col8);
+#else
+    const int kq = lv >> 4, col = lv & 15;
     const double* w = wsb + (long)l * Ws<NP>::SLOT;
     s.a = load_d(Am + (long)l * NN, kq, col);
     s.y = load_d(Ym + (long)l * NN, kq, col);
@@ -749,11 +809,25 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     s.k = kk[l * NP + col];
     s.e = 0.0;
     s.e = Ek[l * NP + col];
+#endif
     return s;
   };
   v4f64 w1, w2;
   // (what the turn needs from memory -- the first operand set included -- is requested ahead of the window's fill: one
   //  memory latency for all of it)
+#if RTD_BC_SADDR
+  const unsigned col8 = (unsigned)col << 3;
+  const double kL = ldg_u(kk + Lm1 * NP, col8);
+  double eL_g = 0.0;
+  eL_g = ldg_u(Ek + Lm1 * NP, col8);
+  double attL = 0.0, buL = 0.0, bdL = 0.0;
+  if (beam && um) {
+    const unsigned i8 = (unsigned)(4 * (col & 3) + kq) << 3;  // the element of u^m a lane col < 4 stages
+    attL = d.att[(long)c * (L + 1) + L];
+    buL = ldg_u(Bv + Lm1 * Q, i8);
+    bdL = ldg_u(Bv + Lm1 * Q, i8, 8 * NP);
+  }
+#else
   const double kL = kk[Lm1 * NP + col];
   double eL_g = 0.0;
   eL_g = Ek[Lm1 * NP + col];
@@ -763,6 +837,7 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     buL = Bv[Lm1 * Q + 4 * (col & 3) + kq];
     bdL = Bv[Lm1 * Q + NP + 4 * (col & 3) + kq];
   }
+#endif
   BwSet s0 = {};
   if (Lm1 > 0) s0 = load_set(Lm1 - 1);
   fill_all(max(L - W, 0), true);
@@ -778,8 +853,14 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
         up = fma(buL, attL, up);
         dn = fma(bdL, attL, dn);
         if (iso) {
+#if RTD_BC_SADDR
+          const double* vL = vbp + ((long)Lm1 * 4 + 2) * NP;  // vedge(Lm1, true, .)
+          up += ldg_u(vL, (unsigned)i << 3);
+          dn += ldg_u(vL, (unsigned)i << 3, 8 * NP);
+#else
           up += vedge(Lm1, true, i);
           dn += vedge(Lm1, true, NP + i);
+#endif
         }
         sOut[32 + i] = up;
         sOut[32 + NP + i] = dn;

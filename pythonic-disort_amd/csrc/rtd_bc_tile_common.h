@@ -61,6 +61,50 @@ __device__ __forceinline__ v4f64 col_to_row(const double vc, const int rowbase, 
   r[3] = bperm((rowbase | (12 + kq)) << 2, vc);
   return r;
 }
+// Global accesses of rtd_bc_mfma_kernel (RTD_BC_SADDR) as "wave-uniform base + constant + 32-bit lane offset": the address is
+// then an SGPR pair, an unsigned VGPR offset and an immediate inside the memory instruction (global_load_dwordx2 v, v_off,
+// s[b:b+1] offset:imm) -- no 64-bit per-lane address is formed by vector instructions, and a layer's base advances on the scalar
+// unit.  `ub` must be wave-uniform (a kernel argument plus expressions of blockIdx and loop counters); the constant is added to
+// it in 64 bits, so that the lane offset stays a plain zero-extended register.  Three lane offsets serve every access of the
+// kernel: D-layout matrix element q of a lane is 8 lane + 512 q, a column-form element 8 col, a row-form element q 8 kq + 32 q.
+struct LaneOff {
+  unsigned lane8, col8, kq8;  // bytes
+};
+__device__ __forceinline__ LaneOff lane_offsets(const int lane) {
+  LaneOff o;
+  o.lane8 = (unsigned)lane << 3;
+  o.col8 = ((unsigned)lane & 15u) << 3;
+  o.kq8 = ((unsigned)lane >> 4) << 3;
+  return o;
+}
+// (a copy of a lane offset that the compiler takes for a new value: its zero-extension then stays in the basic block of the
+//  access -- the register-offset form is matched block by block, and an extension made in another block arrives as a 64-bit pair)
+__device__ __forceinline__ unsigned block_local(unsigned v) {
+  asm("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ double ldg_u(const double* ub, const unsigned off, const long cbytes = 0) {
+  return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(ub) + cbytes + (size_t)off);
+}
+__device__ __forceinline__ void stg_u(double* ub, const unsigned off, const long cbytes, const double v) {
+  *reinterpret_cast<double*>(reinterpret_cast<char*>(ub) + cbytes + (size_t)off) = v;
+}
+__device__ __forceinline__ v4f64 load_d_u(const double* ub, const unsigned lane8) {  // row-major 16 x 16 matrix -> D layout
+  v4f64 x;
+  x[0] = ldg_u(ub, lane8, 0);
+  x[1] = ldg_u(ub, lane8, 512);
+  x[2] = ldg_u(ub, lane8, 1024);
+  x[3] = ldg_u(ub, lane8, 1536);
+  return x;
+}
+__device__ __forceinline__ v4f64 load_row_u(const double* ub, const unsigned kq8) {  // a 16-vector in row form
+  v4f64 x;
+  x[0] = ldg_u(ub, kq8, 0);
+  x[1] = ldg_u(ub, kq8, 32);
+  x[2] = ldg_u(ub, kq8, 64);
+  x[3] = ldg_u(ub, kq8, 96);
+  return x;
+}
 __device__ __forceinline__ double readlane_f64(const double v, const int lane_uniform) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane_uniform), __builtin_amdgcn_readlane(__double2loint(v), lane_uniform));
 }
