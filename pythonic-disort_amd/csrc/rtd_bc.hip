@@ -65,19 +65,12 @@ namespace {
 #ifndef RTD_GJ_GROWTH
 #define RTD_GJ_GROWTH 64.0
 #endif
-#ifndef RTD_GJ_FMAC_DPP
-#define RTD_GJ_FMAC_DPP 1
-#endif
-// RTD_BC_SADDR: the kernel's global loads and stores in the two sweeps, at the turn and in the flush take a wave-uniform base
-// and a 32-bit lane offset (ldg_u / stg_u, rtd_bc_tile_common.h) instead of a per-lane 64-bit pointer.  Addresses only: the
-// order and the number of the memory operations -- what the counted waits rest on -- and every floating-point operation are
-// those of the RTD_BC_SADDR=0 form (tests/test_gpu_bc32_bits.py holds the results to the bit).  (One exception, outside the
-// sweeps' counted waits: the flush's two predicated stores are written that way too, and the compiler then sinks them into ONE
+// The kernel's global loads and stores in the two sweeps, at the turn and in the flush take a wave-uniform base and a 32-bit
+// lane offset (ldg_u / stg_u, rtd_bc_tile_common.h) instead of a per-lane 64-bit pointer: -8 % VALU, +1.6 % headline against
+// the per-lane-pointer form, the same memory operations in the same order and the same results to the bit
+// (tests/test_gpu_bc32_bits.py).  (The flush's two predicated stores, written that way too, are sunk by the compiler into ONE
 // store per staged row with a selected per-lane base -- the same lanes and bytes; the flush waits for vmcnt(0) itself.  The
 // window fills keep their per-lane pointers.  HISTORY.md: "Scalar-base addressing in the 32-stream BC kernel".)
-#ifndef RTD_BC_SADDR
-#define RTD_BC_SADDR 1
-#endif
 template <int K, int Q0, int Q1>
 struct FmacRows {  // v[q] -= bcast_K(v[q]) * f for q in [Q0, Q1)
   static __device__ __forceinline__ void run(double (&v)[4], const double f) {
@@ -100,9 +93,8 @@ struct GjFast {
     const double rp = r0 * (2.0 - xk * r0);
     const double f = (col == K) ? 1.0 - rp : x * rp;
     bad |= (col > K && fabs(f) > RTD_GJ_GROWTH) ? 1 : 0;  // a zero pivot shows up as a non-finite result (checked by the caller)
-#if RTD_GJ_FMAC_DPP
     // v -= bcast_K(v) * f as ONE instruction per register: v_fmac_f64 with a row_newbcast DPP source (the only DPP control
-    // the DP ALU has), the source being the accumulator itself.  The compiler's hazard recogniser does not see VALU writes
+    // the DP ALU has), the source being the accumulator itself (settled in round 3 against an FMA on a bcast16 copy).  The compiler's hazard recogniser does not see VALU writes
     // made inside inline asm; a DPP read needs two wait states after a VALU write of the same VGPR: every register
     // touched here was last written by the previous step's block (>= 9 instructions back), and the block ends with the
     // wait states that cover the compiler's own DPP / permute reads of ta in the next step.  `volatile` keeps the blocks
@@ -111,17 +103,6 @@ struct GjFast {
     FmacRows<K, QK, 4>::run(ta, f);
     FmacRows<K, 0, NB>::run(tb, f);
     asm volatile("v_fmac_f64_dpp %0, -%0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf\n\ts_nop 1" : "+v"(tv) : "v"(f), "n"(K));
-#else
-    static_for<QK, 4>([&](auto qc) {  // rows below 4 QK are finished: the pivot column is zero there
-      constexpr int q = decltype(qc)::value;
-      ta[q] = fma(-f, bcast16<K>(ta[q]), ta[q]);
-    });
-    static_for<0, NB>([&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-      tb[q] = fma(-f, bcast16<K>(tb[q]), tb[q]);
-    });
-    tv = fma(-f, bcast16<K>(tv), tv);
-#endif
     GjFast<NB, K + 1>::run(ta, tb, tv, bad, col);
   }
 };
@@ -178,7 +159,7 @@ struct GjPiv {
 
 // Four wavefronts per SIMD: <= 128 registers and <= 10 KB of LDS each, so the kernel prefetches one layer ahead, forms the
 // interface products one after the other (one accumulator set live), takes exp(-k dtau) from memory, saves t^T once and
-// rotates two operand sets in the backward sweep (128 VGPRs, 13 dwords spilled outside the two loops with RTD_BC_SADDR, 22 without -- profiles/bc32_diet/kernel_resources*.json; 9.8 KB).  The kernel
+// rotates two operand sets in the backward sweep (128 VGPRs, 13 dwords spilled outside the two loops -- profiles/bc32_diet/kernel_resources.json; 9.8 KB).  The kernel
 // is bound by the latency of its dependent chains: a three-wavefront form (two layers of prefetch, the products side by
 // side, exp(-k dtau) in the LDS window: 168 VGPRs, 12.7 KB; removed in round 3) took 4.19-4.25 ms per 2 048 cfg4 columns
 // against this form's 4.08-4.11 ms, and padded to 7 / 9 / 12 wavefronts per CU 5.46 / 4.82 / 4.33 ms.
@@ -201,18 +182,19 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
   const bool iso = d.Ns > 0 && mg == 0;
   const bool beam = d.beam != 0;
   const double mu0 = beam ? d.mu0[c] : 1.0;
-  // careful: this chain takes the column-pivoted elimination throughout (GjPiv, registers) -- the rule of chain_needs_pivoting,
-  // or the test hook RTD_BC_FORCE_PIVOT=2 for every chain.  force_redo (RTD_BC_FORCE_PIVOT=1): every speculative elimination is
+  // careful: this chain takes the column-pivoted elimination throughout (GjPiv, registers) -- a mode-0 chain with a tiny eigenvalue,
+  // thermal source or not (chain_needs_pivoting), or the test hook RTD_BC_FORCE_PIVOT=2 for every chain.  force_redo (RTD_BC_FORCE_PIVOT=1): every speculative elimination is
   // declared failed and redone by pivoted_lds, the path of the rare real failures (the suite runs under both).
-  const int careful = chain_needs_pivoting(d, RTD_BC_CAREFUL_ALL_MODE0 ? mg == 0 : iso, kk, L, NP) | ((d.flags >> 2) & 1);
+  const int careful = chain_needs_pivoting(d, mg == 0, kk, L, NP) | ((d.flags >> 2) & 1);
   const int force_redo = d.flags & 1;
   // thermal particular solution of layer l at one of the layer's own boundaries (top / bottom), streams idx in [0, 2 NP): the values
   // the eigen kernel left in vb (it holds the polynomial coefficients about the layer's top, rtd_dd.h) -- no polynomial is evaluated here
   const double* vbp = d.vb + (long)c * L * 4 * NP;
   auto vedge = [&](int l, bool bottom, int idx) { return vbp[((long)l * 4 + (bottom ? 2 : 0)) * NP + idx]; };
-  // (kq, col are passed in so that the loops can hand over an opaque copy of the lane index: the compiler then
-  //  rebuilds the few address VGPRs per iteration instead of keeping dozens of hoisted ones alive and spilling)
-  auto load_d = [](const double* p, const int kq, const int col) {  // row-major 16 x 16 matrix -> D layout
+  // Per-lane-pointer loads: the prologue's and the bottom boundary's global reads and every LDS read (the sweeps' global accesses
+  // are load_d_u / load_row_u).  (kq is passed in so that the loops can hand over an opaque copy of the lane index: the compiler
+  // then rebuilds the few address VGPRs per iteration instead of keeping dozens of hoisted ones alive and spilling)
+  auto load_d =[](const double* p, const int kq, const int col) {  // row-major 16 x 16 matrix -> D layout
     v4f64 x;
     x[0] = p[kq * NP + col];
     x[1] = p[(4 + kq) * NP + col];
@@ -433,7 +415,6 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     const int ln = min(l + 1, Lm1), l2 = min(l + 2, Lm1);
     v4f64 a2 = a1, y2 = y1, e1r_g = a1;
     double k2c = k1c, e0c_g = 0.0;
-#if RTD_BC_SADDR
     const LaneOff lo = lane_offsets(lv);
     {  // one layer ahead: consumed behind this iteration's elimination
       a1 = load_d_u(Am + (long)ln * NN, lo.lane8);
@@ -442,15 +423,6 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
       e0c_g = ldg_u(Ek + l * NP, lo.col8);
       e1r_g = load_row_u(Ek + ln * NP, lo.kq8);
     }
-#else
-    {  // one layer ahead: consumed behind this iteration's elimination
-      a1 = load_d(Am + (long)ln * NN, kq, col);
-      y1 = load_d(Ym + (long)ln * NN, kq, col);
-      k1c = kk[ln * NP + col];
-      e0c_g = Ek[l * NP + col];
-      e1r_g = load_row(Ek + ln * NP, kq);
-    }
-#endif
     if (ln >= wb + W) fill(l, false);
     RTD_STAMP();  // 4 l + 1: loop top (register rotation, loads issued)
     const int r0 = l - wb, r1 = ln - wb;
@@ -500,7 +472,6 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     RTD_STAMP();  // 4 l + 2: elimination
     if (l == Lm1) break;
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the loads of this iteration, before the stores go out
-#if RTD_BC_SADDR
     // (S, rho_b and s lie 4 096 ... 6 528 bytes into the slot, past the 13-bit immediate: the scalar base is taken at S through an
     //  opaque byte offset, or the compiler folds the constants back into one and builds the address in vector registers after
     //  all.  The offset, not the pointer: a pointer out of an asm statement is a flat one)
@@ -510,12 +481,6 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) stg_u(wS, block_local(lo.lane8), 512 * q, tb[q]);  // element [4 q + kq][col]
     if (kq == 0) stg_u(wS, block_local(lo.col8), 8 * (Ws<NP>::SV - Ws<NP>::S), tv);
-#else
-    double* ws = wsb + (long)l * Ws<NP>::SLOT;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ws[Ws<NP>::S + (4 * q + kq) * NP + col] = tb[q];
-    if (kq == 0) ws[Ws<NP>::SV + col] = tv;
-#endif
     {
       // the same quantities with one accumulator set live at a time (Y_l is scaled in place: it is not used again)
       v4f64 a1s;
@@ -540,11 +505,7 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
         rt = 0.25 * sum_kq(rt);
         rb = 0.25 * sum_kq(rb);
       }
-#if RTD_BC_SADDR
       if (kq == 0) stg_u(wS, block_local(lo.col8), 8 * (Ws<NP>::RB - Ws<NP>::S), rb);
-#else
-      if (kq == 0) ws[Ws<NP>::RB + col] = rb;
-#endif
       const double e0c = e0c_g;
       v4f64 he;
 #pragma unroll
@@ -712,20 +673,12 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     for (int k2 = 0; k2 < nstage; ++k2) {
       const long row = ltop - k2;
       const double v = sOut[k2 * 64 + lane];
-#if RTD_BC_SADDR
       const unsigned lane8 = (unsigned)lane << 3;
       if (lane < 32) {
         if (row < L) stg_u(coef + row * Q, lane8, 0, v);
       } else if (um) {
         stg_u(um + row * Q, lane8, -8 * 32, v);  // element lane - 32
       }
-#else
-      if (lane < 32) {
-        if (row < L) coef[row * Q + lane] = v;
-      } else if (um) {
-        um[row * Q + lane - 32] = v;
-      }
-#endif
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();
@@ -785,7 +738,6 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     int lv = lane;
     asm volatile("" : "+v"(lv));
     BwSet s;
-#if RTD_BC_SADDR
     const LaneOff lo = lane_offsets(lv);
     s.a = load_d_u(Am + (long)l * NN, lo.lane8);
     s.y = load_d_u(Ym + (long)l * NN, lo.lane8);
@@ -798,24 +750,11 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     s.k = ldg_u(kk + l * NP, lo.col8);
     s.e = 0.0;
     s.e = ldg_u(Ek + l * NP, lo.col8);
-#else
-    const int kq = lv >> 4, col = lv & 15;
-    const double* w = wsb + (long)l * Ws<NP>::SLOT;
-    s.a = load_d(Am + (long)l * NN, kq, col);
-    s.y = load_d(Ym + (long)l * NN, kq, col);
-    s.h = load_d(w + Ws<NP>::S, kq, col);
-    s.sl = w[Ws<NP>::SV + col];
-    s.rb = w[Ws<NP>::RB + col];
-    s.k = kk[l * NP + col];
-    s.e = 0.0;
-    s.e = Ek[l * NP + col];
-#endif
     return s;
   };
   v4f64 w1, w2;
   // (what the turn needs from memory -- the first operand set included -- is requested ahead of the window's fill: one
   //  memory latency for all of it)
-#if RTD_BC_SADDR
   const unsigned col8 = (unsigned)col << 3;
   const double kL = ldg_u(kk + Lm1 * NP, col8);
   double eL_g = 0.0;
@@ -827,17 +766,6 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     buL = ldg_u(Bv + Lm1 * Q, i8);
     bdL = ldg_u(Bv + Lm1 * Q, i8, 8 * NP);
   }
-#else
-  const double kL = kk[Lm1 * NP + col];
-  double eL_g = 0.0;
-  eL_g = Ek[Lm1 * NP + col];
-  double attL = 0.0, buL = 0.0, bdL = 0.0;
-  if (beam && um) {
-    attL = d.att[(long)c * (L + 1) + L];
-    buL = Bv[Lm1 * Q + 4 * (col & 3) + kq];
-    bdL = Bv[Lm1 * Q + NP + 4 * (col & 3) + kq];
-  }
-#endif
   BwSet s0 = {};
   if (Lm1 > 0) s0 = load_set(Lm1 - 1);
   fill_all(max(L - W, 0), true);
@@ -853,14 +781,9 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
         up = fma(buL, attL, up);
         dn = fma(bdL, attL, dn);
         if (iso) {
-#if RTD_BC_SADDR
           const double* vL = vbp + ((long)Lm1 * 4 + 2) * NP;  // vedge(Lm1, true, .)
           up += ldg_u(vL, (unsigned)i << 3);
           dn += ldg_u(vL, (unsigned)i << 3, 8 * NP);
-#else
-          up += vedge(Lm1, true, i);
-          dn += vedge(Lm1, true, NP + i);
-#endif
         }
         sOut[32 + i] = up;
         sOut[32 + NP + i] = dn;

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(64, 2) void rtd_bc_tile2_kernel(RtdDev d, int* need
   const double mu0 = beam ? d.mu0[c] : 1.0;
   // pivoted throughout (in registers here: the rule of the 32-stream kernel applies, every mode-0 chain with a small eigenvalue),
   // or RTD_BC_FORCE_PIVOT (either value)
-  const int careful = chain_needs_pivoting(d, RTD_BC_CAREFUL_ALL_MODE0 ? mg == 0 : iso, kk, L, NP) | (d.flags & 1) | ((d.flags >> 2) & 1);
+  const int careful = chain_needs_pivoting(d, mg == 0, kk, L, NP) | (d.flags & 1) | ((d.flags >> 2) & 1);
   if ((d.flags & 2) && m % 3 == 0) {  // test hook (RTD_BC_FORCE_HANDOVER): every third Fourier mode's chain goes to the pivoted
     //                                    row-per-lane kernels (by mode, not by chain index: the choice must not depend on the windowing)
     if (lane == 0) {

@@ -61,7 +61,7 @@ __device__ __forceinline__ v4f64 col_to_row(const double vc, const int rowbase, 
   r[3] = bperm((rowbase | (12 + kq)) << 2, vc);
   return r;
 }
-// Global accesses of rtd_bc_mfma_kernel (RTD_BC_SADDR) as "wave-uniform base + constant + 32-bit lane offset": the address is
+// Global accesses of rtd_bc_mfma_kernel's sweeps as "wave-uniform base + constant + 32-bit lane offset": the address is
 // then an SGPR pair, an unsigned VGPR offset and an immediate inside the memory instruction (global_load_dwordx2 v, v_off,
 // s[b:b+1] offset:imm) -- no 64-bit per-lane address is formed by vector instructions, and a layer's base advances on the scalar
 // unit.  `ub` must be wave-uniform (a kernel argument plus expressions of blockIdx and loop counters); the constant is added to
@@ -114,16 +114,11 @@ __device__ __forceinline__ double readlane_f64(const double v, const int lane_un
 // 1 - 1e-6) seventeen orders of magnitude above the field, which is then as good as the RELATIVE accuracy of C.  The speculative
 // elimination accepts multipliers up to 64 (1e6 in the tiled kernel) and loses two to three digits against the pivoted one
 // there (9e-2 against 3e-4 of the field scale on the case of DESIGN.md section 8, the reference: 2e-4); such chains -- mode 0
-// with a thermal source and an eigenvalue below RTD_BC_CAREFUL_K somewhere -- take the pivoted elimination throughout.
+// with an eigenvalue below RTD_BC_CAREFUL_K somewhere -- take the pivoted elimination throughout, in both kernels.
+// (Thermal source or not: round 3 measured the near-conservative beam cases going from <= 1.5e-9 to
+// <= 5e-12 of their 40-digit solutions; pivoting in registers -- GjPiv, GjPivT -- made that cheap enough to be the rule.)
 #ifndef RTD_BC_CAREFUL_K
 #define RTD_BC_CAREFUL_K 0.02
-#endif
-#ifndef RTD_BC_CAREFUL_ALL_MODE0
-#define RTD_BC_CAREFUL_ALL_MODE0 1  /* 32 streams (rtd_bc_mfma_kernel): every mode-0 chain with such an eigenvalue, thermal source or
-                                       not.  Round 3 measured what it buys -- the near-conservative beam cases go from <= 1.5e-9 to
-                                       <= 5e-12 of their 40-digit solutions -- and what it cost with the LDS redo: 219 k -> 71 k col/s on a
-                                       batch with a conservative cloud layer in every column; with GjPiv (registers) it is the default.
-                                       The 64-stream kernel (rtd_bc_tile2_kernel) follows the same switch: it pivots in registers too (GjPivT). */
 #endif
 // Which chain (column c, local mode m: index c M + m) a workgroup takes.  Mode 0 of every column first, then the other modes column
 // by column: the chains that are pivoted throughout (above: mode 0 only) take 3 ... 7 times as long as the others, and handed out in
@@ -136,9 +131,9 @@ __device__ __forceinline__ long chain_of_block(const long b, const int C, const 
   return (r / (M - 1)) * M + 1 + r % (M - 1);
 }
 
-__device__ __forceinline__ int chain_needs_pivoting(const RtdDev& d, const bool iso, const double* kk, const int L, const int np) {
+__device__ __forceinline__ int chain_needs_pivoting(const RtdDev& d, const bool mode0, const double* kk, const int L, const int np) {
   int careful = 0;
-  if (iso) {  // (wave-uniform condition: one chain per wavefront.  The scan is lane-parallel -- one memory latency, then a wave
+  if (mode0) {  // (wave-uniform condition: one chain per wavefront.  The scan is lane-parallel -- one memory latency, then a wave
     //           reduction: a scalar loop over the L np eigenvalues cost a mode-0 chain L np dependent loads, 6 % of its life)
     double kmin = 1e300;
     for (int i = (int)threadIdx.x; i < L * np; i += 64) kmin = fmin(kmin, kk[i]);

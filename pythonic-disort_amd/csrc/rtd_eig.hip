@@ -25,10 +25,6 @@ namespace {
 
 // compiler-only barrier: keeps the scheduler from hoisting a whole unrolled loop's LDS loads
 #define RTD_FENCE() asm volatile("" ::: "memory")
-#ifndef RTD_XOR_DPP
-#define RTD_XOR_DPP 0x818E  /* bit set of the xor masks done by ONE DPP move per dword (1, 2, 3, 7, 8, 15) instead of ds_swizzle:
-                               A/B on one box 6.03 -> 5.94 ms (with bound_ctrl moves; with the old copy-then-move form it lost 2 %) */
-#endif
 
 // DPP control of a lane permutation "lane ^ MASK" inside a 16-lane row that one DPP move can express, else -1:
 // quad permutes for 1, 2, 3; row_half_mirror = ^7; row_ror:8 = ^8; row_mirror = ^15
@@ -44,7 +40,8 @@ __device__ __forceinline__ double xor_lane(double v) {
   if constexpr (MASK >= 32) return __shfl_xor(v, MASK, 64);  // across the halves of the wavefront: ds_bpermute (NP = 64 only)
   int lo = __double2loint(v), hi = __double2hiint(v);
   constexpr int ctrl = dpp_xor_ctrl(MASK);
-  if constexpr (ctrl >= 0 && ((RTD_XOR_DPP >> MASK) & 1)) {  // one VALU move per dword, no LDS crossbar (RTD_XOR_DPP = bit set of masks)
+  if constexpr (ctrl >= 0) {  // one VALU move per dword, no LDS crossbar: A/B on one box against ds_swizzle for these masks 6.03 -> 5.94 ms
+    //                           (with bound_ctrl moves; with the old copy-then-move form it lost 2 %)
     lo = __builtin_amdgcn_update_dpp(0, lo, ctrl, 0xF, 0xF, true);
     hi = __builtin_amdgcn_update_dpp(0, hi, ctrl, 0xF, 0xF, true);
   } else {  // ds_swizzle bit-mode: and = 0x1f, or = 0, xor = MASK
@@ -96,36 +93,12 @@ __device__ __forceinline__ double fast_rcp(double x) {
   y = y * (2.0 - x * y);
   return y;
 }
-// one Newton step from the ~5e-8 hardware seeds: ~4e-15 relative (tools/hiptests/seed_accuracy.hip), enough for
-// quantities that only steer a rotation angle
+// one Newton step from the ~5e-8 hardware seed: ~4e-15 relative (tools/hiptests/seed_accuracy.hip), enough for the
+// cosine of a Jacobi rotation (see PairStep)
 __device__ __forceinline__ double approx_rsqrt(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   return y * (1.5 - 0.5 * x * y * y);
 }
-__device__ __forceinline__ double approx_rcp(double x) {
-  const double y = __builtin_amdgcn_rcp(x);
-  return y * (2.0 - x * y);
-}
-
-#ifndef RTD_JAC_F32_ANGLE
-#define RTD_JAC_F32_ANGLE 1  /* rotation angle of the pair-layout sweeps from float arithmetic (see PairStep) */
-#endif
-#ifndef RTD_JAC_SMALL_ANGLE
-#define RTD_JAC_SMALL_ANGLE 1  /* pair-layout sweeps, NP <= 16: steps in which the whole wavefront has |t| < 2^-27 rotate with c = 1 exactly (see PairStep) */
-#endif
-#ifndef RTD_CHOL_FMAC_DPP
-#define RTD_CHOL_FMAC_DPP 1  /* Cholesky trailing updates as ONE v_fmac_f64_dpp (row_newbcast) per element, NP = 16 */
-#endif
-
-#ifndef RTD_DPP_MERGE
-#define RTD_DPP_MERGE 1  /* NP = 16: levels 8 and 4 of the transposed reductions and the pair-layout exchange as bank-masked DPP merges (dpp_merge) */
-#endif
-#ifndef RTD_CHOL_EXEC_PICK
-#define RTD_CHOL_EXEC_PICK 1  /* NP = 16: a Cholesky step's multiplier and diagonal under constant EXEC masks (chol_pick16), no compare or select */
-#endif
-
-constexpr bool kDppMerge = RTD_DPP_MERGE != 0;
-constexpr bool kCholPick16 = RTD_CHOL_FMAC_DPP != 0 && RTD_CHOL_EXEC_PICK != 0;
 
 #ifndef RTD_EIGEN32_WAVES
 #define RTD_EIGEN32_WAVES 2  /* waves per SIMD of the 64-stream eigen kernel (256 VGPRs; the spill counts of every kernel: profiles/rNN_kernel_resources.json, tools/kernel_resources.py; 1: 278 VGPRs) */
@@ -311,13 +284,13 @@ template <int NP, int K>
 struct CholStep {
   static __device__ __forceinline__ void run(double (&col)[NP], double& diag, double& f, const int j) {
     const double akk = bcast_lane<NP, K>(col[K]);
-    if constexpr (kCholPick16 && NP == 16) {
+    if constexpr (NP == 16) {
       chol_pick16<K, K == NP - 1>(f, diag, col[K], fast_rcp(akk), akk);
     } else {
       f = (j > K) ? col[K] * fast_rcp(akk) : 0.0;
       diag = (j == K) ? akk : diag;
     }
-    if constexpr (RTD_CHOL_FMAC_DPP && NP == 16) {
+    if constexpr (NP == 16) {
       // col[i] -= bcast_K(col[i]) * f in one instruction: the DP-ALU DPP form exists for row_newbcast only (the DPP
       // source is the accumulator itself).  A VALU write of a VGPR needs two wait states before a DPP read of it: the
       // elements were last written by step K - 1's updates, at least NP - K instructions back; `f` is not a DPP operand.
@@ -559,7 +532,7 @@ __device__ __forceinline__ double cholesky_columns(double (&col)[NP], const int 
   const double rinv = fast_rsqrt(diag);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    if constexpr (kCholPick16 && NP == 16) col[i] *= rinv;  // (zero above the diagonal since step i: chol_pick16)
+    if constexpr (NP == 16) col[i] *= rinv;  // (zero above the diagonal since step i: chol_pick16)
     else col[i] = (i >= j) ? col[i] * rinv : 0.0;
   }
   return rinv;
@@ -586,13 +559,8 @@ __device__ __forceinline__ ProbId locate(const RtdDev& d, const int tx = threadI
   // Workgroups are handed out mode by mode (all columns of mode 0, then of mode 1, ...): the sweep count falls with the Fourier mode
   // (5.8 sweeps at m = 0, 1.8 at m = 31 on cfg4), so the longest problems start first and the launch ends on its shortest ones
   // instead of on the last column's mode 0; the mode's table rows are shared by everything that runs at the same time.
-#ifdef RTD_EIG_COLUMN_MAJOR  /* A/B builds: the order of rounds 1-5 */
-  p.m = (int)(cmi_b % d.M);
-  p.c = (int)(cmi_b / d.M);
-#else
   p.m = (int)(cmi_b / d.C);
   p.c = (int)(cmi_b % d.C);
-#endif
   p.mg = d.m0 + d.mstep * p.m;
   const long cmi = (long)p.c * d.M + p.m;
   if (d.nsel > 0) chunk = d.chunk_sel[(long)p.c * d.nsel + chunk];  // (wave-uniform) -1: this entry of the list is empty
@@ -655,7 +623,7 @@ __device__ __forceinline__ int xor_lane_i(int v) {
 }
 
 template <int NP, int S>
-struct PairStep {
+struct PairStep {  // NP <= 16 (NP >= 32: FastPairStep below)
   static constexpr int H = NP / 2;
   static __device__ __forceinline__ void run(double (&xh)[H], double (&yh)[H], double& ax, double& ay, int& ix, int& iy,
                                              const int p, unsigned long long& notconv) {
@@ -680,7 +648,6 @@ struct PairStep {
     // gamma = 0 (decoupled or already orthogonal columns, also with equal norms) at t = 0, c = 1 without a 0/0.
     const double delta = ay - ax;
     const double g2 = 2.0 * gamma;
-#if RTD_JAC_F32_ANGLE
     // The angle only steers the iteration: a t that is 1e-7 off leaves 1e-7 of the pair's inner product behind, far below
     // what the sweep test asks for (the test is made BEFORE the rotation).  So t comes from float arithmetic with the
     // hardware's rsq / rcp and no Newton step (eigenvalues here lie between 1e-3 and 1e5: no float range issue; a
@@ -692,13 +659,6 @@ struct PairStep {
     const float denf = df + copysignf(rhof, df);
     const float tf = gf * __builtin_amdgcn_rcpf(denf);
     const double tt = (double)tf;
-#else
-    const double r2 = fma(delta, delta, fma(g2, g2, 1e-280));
-    const double rho = r2 * approx_rsqrt(r2);
-    const double den = delta + copysign(rho, delta);
-    const double tt = g2 * approx_rcp(den);
-    const float tf = (float)tt;
-#endif
     // the stop test as a lane mask, accumulated on the scalar unit: only "any lane, any step" is ever asked.  (The per-lane flag
     // was that already in the straight-line sweep; between the branches of the small-angle steps the compiler moved all 15
     // compares, with the gamma, ax and ay they read, to the end of the sweep: 90 registers held for nothing.)
@@ -709,7 +669,7 @@ struct PairStep {
     // whole wavefront (a lane mask tested on the scalar unit; a NaN counts as large): when every pair is below the bound, the
     // rsq + Newton chain is skipped and the steps that hand on Y everywhere rotate as x - t y, y + t x, without the products
     // by 1.  The same bits as the general form whenever the hardware's rsq(1.0) is 1.0; one rounding of c otherwise.
-    const bool small = RTD_JAC_SMALL_ANGLE != 0 && __builtin_amdgcn_ballot_w64(!(fabsf(tf) < 0x1p-27f)) == 0;
+    const bool small = __builtin_amdgcn_ballot_w64(!(fabsf(tf) < 0x1p-27f)) == 0;
     // The two forms meet in xn, yn, arrays of the step's own whose every index is a constant of the source (pack expansions, not
     // loops): those become scalars before anything is inlined or unrolled.  Written into xh, yh inside the branches -- or into
     // local arrays indexed by loops -- the forms met in whole columns, register tuples of 2 H dwords each, copied at the join.
@@ -759,9 +719,6 @@ struct PairStep<NP, NP - 1> {  // the last step of a sweep is step NP - 2
                                              unsigned long long&) {}
 };
 
-#ifndef RTD_JAC_FAST
-#define RTD_JAC_FAST 1  /* NP >= 32: scaled ("fast") rotations in the pair-layout sweeps, see FastPairStep */
-#endif
 // The same step with SCALED rotations, for NP >= 32.  The lane keeps its halves of the two columns as x = sx xs, y = sy ys (xs, ys
 // stored, sx, sy per-column scalars) and applies (x, y) <- c (x - t y, y + t x) as
 //     xs <- xs - (t sy / sx) ys,   ys <- ys + (t sx / sy) xs,   sx <- c sx,   sy <- c sy :
@@ -1253,7 +1210,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     double xh[H], yh[H];
 #pragma unroll
     for (int i = 0; i < H; ++i) {  // columns p and p + H start in slot p: trade the halves with lane ^ H
-      if constexpr (kDppMerge && NP == 16) {  // u is the lane's bit 3, two whole banks: merged in place by bank-masked moves, no select (dpp_merge)
+      if constexpr (NP == 16) {  // u is the lane's bit 3, two whole banks: merged in place by bank-masked moves, no select (dpp_merge)
         xh[i] = dpp_merge<0x128, 0xC>(copy64(w[i]), w[H + i]);
         yh[i] = dpp_merge<0x128, 0x3>(w[H + i], w[i]);
       } else {
@@ -1273,7 +1230,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       }
       ax += xor_lane<H>(ax);
       ay += xor_lane<H>(ay);
-      if constexpr (RTD_JAC_FAST && NP >= 32) {
+      if constexpr (NP >= 32) {  // scaled rotations (FastPairStep)
         int notconv = 0;
         double sx = 1.0, sy = 1.0, rx = 1.0, ry = 1.0;
         FastPairStep<NP, 0>::run(xh, yh, ax, ay, ix, iy, p, notconv, sx, sy, rx, ry);
@@ -1297,7 +1254,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     // back to one column per lane: lane (p, 0) takes column X of its slot, lane (p, 1) column Y ...
 #pragma unroll
     for (int i = 0; i < H; ++i) {
-      if constexpr (kDppMerge && NP == 16) {
+      if constexpr (NP == 16) {
         w[i] = dpp_merge<0x128, 0xC>(copy64(xh[i]), yh[i]);
         w[H + i] = dpp_merge<0x128, 0x3>(yh[i], xh[i]);
       } else {
@@ -1442,7 +1399,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       const double tq = dot_bcast16(txd, ya) * k2;  // lane e: k_e^2 (Y^T v0)_e
 #pragma unroll
       for (int i = 0; i < NP; ++i) x[i] = ya[i] * tq;
-      const double qv = transpose_reduce<NP, kDppMerge>(x, j);  // Qm v0 = Y k^2 Y^T v0 (exact for the rotated columns)
+      const double qv = transpose_reduce<NP, true>(x, j);  // Qm v0 = Y k^2 Y^T v0 (exact for the rotated columns)
       const double rmu0 = fast_rcp(mu0);
       const double rhat = 2.0 * T_j * xo * invmu_j * rmu0 - qv;
       double lc[NP];  // column j of L (zero above the diagonal)
@@ -1452,7 +1409,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
       const double h = dot_bcast16(g, zc) * fast_rcp(rmu0 * rmu0 - k2);  // h = Z^T g / (1/mu0^2 - k^2)
 #pragma unroll
       for (int i = 0; i < NP; ++i) x[i] = ya[i] * h;
-      sh = transpose_reduce<NP, kDppMerge>(x, j);  // shat = L^-T Z h = Y h
+      sh = transpose_reduce<NP, true>(x, j);  // shat = L^-T Z h = Y h
       const double e = dot_bcast16(sh, lc);        // t = L^T shat
       double lr[NP];  // row j of L
 #pragma unroll
@@ -1638,8 +1595,8 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
           xu[i] = py - pa;
           xd[i] = py + pa;
         }
-        up = transpose_reduce<NP, kDppMerge && NP == 16>(xu, j) * rT;
-        dn = transpose_reduce<NP, kDppMerge && NP == 16>(xd, j) * rT;
+        up = transpose_reduce<NP, NP == 16>(xu, j) * rT;
+        dn = transpose_reduce<NP, NP == 16>(xd, j) * rT;
       }
       if (valid && act) {
         double* dq = d.dq + (((long)c * d.L + l) * d.Ns + q) * 2 * NP;
@@ -1735,12 +1692,9 @@ void rtd_launch_eig(const RtdDev& d, hipStream_t s, int part) {
   const dim3 grid((unsigned)((long)d.C * d.M * (d.nsel > 0 ? d.nsel : (d.ln + gpw - 1) / gpw)));
   // RTD_EIG_MFMA=1: the assembly of Pm, Qm on the matrix cores (NP = 16; A/B runs and a regression test)
   static const bool mfma = getenv("RTD_EIG_MFMA") != nullptr;
-#ifndef RTD_EIG_LDS_PAD
-#define RTD_EIG_LDS_PAD 0  /* profiling builds only: dynamic LDS requested per workgroup, caps the eigen kernel's wavefronts per CU */
-#endif
-#define RTD_EIG_CASE(NPV)                                                                        \
-  case NPV:                                                                                      \
-    hipLaunchKernelGGL((rtd_eigen_kernel<NPV, 2>), grid, dim3(64), RTD_EIG_LDS_PAD, s, d);       \
+#define RTD_EIG_CASE(NPV)                                                          \
+  case NPV:                                                                        \
+    hipLaunchKernelGGL((rtd_eigen_kernel<NPV, 2>), grid, dim3(64), 0, s, d);       \
     break;
   switch (d.NP) {
     case 4:  // 2 ... 8 streams: the one-lane-per-problem kernel (rtd_eig_small.hip)

@@ -1,4 +1,4 @@
-"""The small-angle form of the eigen kernel's Jacobi step (PairStep, RTD_JAC_SMALL_ANGLE in csrc/rtd_eig.hip) -- run with
+"""The small-angle form of the eigen kernel's Jacobi step (PairStep in csrc/rtd_eig.hip) -- run with
 ``-m gpu`` on an MI355X.
 
 A step takes that form when EVERY pair of the wavefront has |t| < 2^-27.  The columns here have four layers, so that one

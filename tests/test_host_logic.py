@@ -111,6 +111,20 @@ def test_library_reads_only_the_documented_environment():
                 assert name in {"RTD_LIB", "RTD_CTL_DIR", "RTD_CTL_TIMEOUT"}, (f, name)  # (_control.py: where ranks meet, how long they wait)
 
 
+def test_compile_time_overrides_are_the_documented_ones():
+    """A settled A/B form is deleted, not kept behind a macro: every RTD_* name that csrc/ tests in the preprocessor is a numeric
+    tunable or a stamp build listed in DESIGN.md, "Compile-time overrides", and that list names nothing the sources do not test."""
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("Compile-time overrides\n"):].split("\n## ")[0]
+    documented = set(re.findall(r"^\* `(RTD_[A-Z0-9_]+)`", section, flags=re.M))
+    csrc = os.path.join(ROOT, "pythonic-disort_amd", "csrc")
+    guarded = set()
+    for f in os.listdir(csrc):
+        for line in re.findall(r"^\s*#\s*(?:ifndef|ifdef|if|elif)\b(.*)$", open(os.path.join(csrc, f)).read(), flags=re.M):
+            guarded |= set(re.findall(r"\bRTD_[A-Z0-9_]+", line))
+    assert guarded == documented, (guarded ^ documented)
+
+
 def _kw(tid="9c"):
     return goldens.load(tid)[0]["kwargs"]
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """NumPy replay of the eigen kernel's one-sided Jacobi iteration on cfg4 problems (CPU; no GPU needed): how many of the steps
 a wavefront executes are SMALL-ANGLE steps -- every pair of every problem of the wavefront has |t| below a threshold, so
-that fma(t, t, 1.0) is 1.0 and the rotation needs neither c nor the products by it (PairStep, RTD_JAC_SMALL_ANGLE in
+that fma(t, t, 1.0) is 1.0 and the rotation needs neither c nor the products by it (PairStep in
 csrc/rtd_eig.hip).  The prediction that HISTORY.md sets beside the measured counters.
 
 Built from tools/jacobi_convergence.py (the same F = L^T R and the same stop rule) with three things closer to the device:
@@ -50,7 +50,7 @@ def step_maxima(W, sweeps=10, butterfly=True):
             gam, ax, ay = np.sum(x * y, 1), np.sum(x * x, 1), np.sum(y * y, 1)
             cmax[k, s] = np.max(gam * gam / (ax * ay), 1)
             delta, g2 = ay - ax, 2 * gam
-            if butterfly:  # the kernel's float angle (RTD_JAC_F32_ANGLE)
+            if butterfly:  # the kernel's float angle (PairStep)
                 df, gf = delta.astype(np.float32), g2.astype(np.float32)
                 r2 = df * df + (gf * gf + np.float32(1e-36))
                 t = (gf / (df + np.copysign(np.sqrt(r2), df))).astype(np.float64)
