@@ -45,24 +45,46 @@ inline hipError_t hipMalloc(double** p, size_t n) { return hipMalloc((void**)p, 
 template <typename T>
 inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
 
+// Call trace (tests/cpu/plan_trace_host_main.cpp, built with -DFAKE_HIP_TRACE; defined in host_asan_shadow.cpp): every runtime call
+// below and every launch appends one text line to a log.  Streams and events appear as ordinals in order of creation (the token
+// holds its ordinal), device pointers as "a<ordinal of the live allocation>+<byte offset>", host pointers not at all.  Without the
+// macro FAKE_TR expands to nothing and this header is what it was.
+#ifdef FAKE_HIP_TRACE
+#include <string>
+void fake_trace(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+std::string fake_dev(const void* p);  // "a3+128", "null", or "?" for an address outside every live allocation
+int fake_token_new();                 // the next stream / event ordinal
+inline int fake_id(const void* token) { return token ? *(const int*)token : -1; }
+inline const char* fake_kind(hipMemcpyKind k) { return k == hipMemcpyHostToDevice ? "H2D" : k == hipMemcpyDeviceToHost ? "D2H" : k == hipMemcpyDeviceToDevice ? "D2D" : "other"; }
+inline void fake_trace_copy(const char* what, void* d, const void* s, size_t n, hipMemcpyKind k, const void* stream, bool async) {
+  const std::string dst = k == hipMemcpyHostToDevice || k == hipMemcpyDeviceToDevice ? fake_dev(d) : "host";
+  const std::string src = k == hipMemcpyDeviceToHost || k == hipMemcpyDeviceToDevice ? fake_dev(s) : "host";
+  if (async) fake_trace("%s %s %zu %s <- %s s%d", what, fake_kind(k), n, dst.c_str(), src.c_str(), fake_id(stream));
+  else fake_trace("%s %s %zu %s <- %s", what, fake_kind(k), n, dst.c_str(), src.c_str());
+}
+#define FAKE_TR(...) __VA_ARGS__
+#else
+#define FAKE_TR(...)
+#endif
+
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory" : "error"; }
-inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
-inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memmove(d, s, n); return hipSuccess; }
-inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)std::malloc(8); return hipSuccess; }
+inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind FAKE_TR(k)) { FAKE_TR(fake_trace_copy("memcpy", d, s, n, k, nullptr, false);) std::memcpy(d, s, n); return hipSuccess; }
+inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind FAKE_TR(k), hipStream_t FAKE_TR(st)) { FAKE_TR(fake_trace_copy("memcpy_async", d, s, n, k, st, true);) std::memmove(d, s, n); return hipSuccess; }
+inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t FAKE_TR(st)) { FAKE_TR(fake_trace("memset_async %d %zu %s s%d", v, n, fake_dev(d).c_str(), fake_id(st));) std::memset(d, v, n); return hipSuccess; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)std::malloc(8); FAKE_TR(*(int*)*s = fake_token_new(); fake_trace("stream_create s%d", fake_id(*s));) return hipSuccess; }
 inline hipError_t hipStreamCreate(hipStream_t* s) { return hipStreamCreateWithFlags(s, 0); }
-inline hipError_t hipStreamDestroy(hipStream_t s) { std::free(s); return hipSuccess; }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)std::malloc(8); return hipSuccess; }
+inline hipError_t hipStreamDestroy(hipStream_t s) { FAKE_TR(fake_trace("stream_destroy s%d", fake_id(s));) std::free(s); return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t FAKE_TR(s)) { FAKE_TR(fake_trace("stream_sync s%d", fake_id(s));) return hipSuccess; }
+inline hipError_t hipStreamWaitEvent(hipStream_t FAKE_TR(s), hipEvent_t FAKE_TR(e), unsigned) { FAKE_TR(fake_trace("stream_wait s%d e%d", fake_id(s), fake_id(e));) return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)std::malloc(8); FAKE_TR(*(int*)*e = fake_token_new(); fake_trace("event_create e%d", fake_id(*e));) return hipSuccess; }
 inline hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
-inline hipError_t hipEventDestroy(hipEvent_t e) { std::free(e); return hipSuccess; }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+inline hipError_t hipEventDestroy(hipEvent_t e) { FAKE_TR(fake_trace("event_destroy e%d", fake_id(e));) std::free(e); return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t FAKE_TR(e), hipStream_t FAKE_TR(s)) { FAKE_TR(fake_trace("event_record e%d s%d", fake_id(e), fake_id(s));) return hipSuccess; }
+inline hipError_t hipEventSynchronize(hipEvent_t FAKE_TR(e)) { FAKE_TR(fake_trace("event_sync e%d", fake_id(e));) return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.001f; return hipSuccess; }
 
 // inter-process handles do not exist here: the tests' stand-in transport (tests/stub/rccl_stub.cpp), built against this header for
@@ -86,4 +108,9 @@ inline void fake_launch(K kernel, dim3 grid, dim3 block, A... args) {
       kernel(args...);
     }
 }
+#ifdef FAKE_HIP_TRACE
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
+  (fake_trace("launch %s grid %u block %u s%d", #kernel, dim3(grid).x, dim3(block).x, fake_id(stream)), fake_launch(kernel, grid, block, __VA_ARGS__))
+#else
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) fake_launch(kernel, grid, block, __VA_ARGS__)
+#endif

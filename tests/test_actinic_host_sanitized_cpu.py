@@ -7,30 +7,10 @@ them thread by thread on heap memory: rtd_plan_fetch_actinic and rtd_plan_fetch_
 evaluate_band, in all three tau-orders, every output pointer NULL in turn, windows of 4 over 15 columns in groups of 5, a plan
 without a beam, the lazily grown buffers, every RTD_ERR_STATE case -- all bounds-checked on the CPU, and every element recomputed
 in long double from the u0 fetched from the same plan, before any of it runs on a GPU."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPU = os.path.join(ROOT, "tests", "cpu")
+import host_program
 
 
 def test_actinic_entry_points_are_clean_under_the_sanitizers(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "actinic_host")
-    srcs = [os.path.join(CPU, "actinic_host_main.cpp"), os.path.join(ROOT, "pythonic-disort_amd", "csrc", "rtd_api.hip"),
-            os.path.join(CPU, "host_asan_shadow.cpp")]
-    subprocess.run([gxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-static-libasan", "-static-libubsan", "-Wno-unused-result", "-I", os.path.join(CPU, "fake_hip"), "-x", "c++", *srcs,
-                    "-o", exe, "-ldl", "-lpthread"], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
-               FAKE_HIP_TOTAL=str(8 << 30))
-    for k in ("RTD_POOL_BYTES", "RTD_WORK_BYTES", "RTD_NO_PIPELINE", "RTD_RCCL_STUB"):
-        env.pop(k, None)
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
+    r = host_program.build_and_run(tmp_path, "actinic_host_main.cpp", "actinic_host")
     assert r.returncode == 0 and "ACTINIC HOST OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]

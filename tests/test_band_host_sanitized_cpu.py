@@ -7,30 +7,10 @@ statically, and run directly.  The mix and reduction kernels are rtd_api.hip's o
 thread on heap memory: the carve of the staging block with and without the thermal description, every optional pointer NULL in
 turn, windows that are no multiple of the spectral points, one and two register chunks of weight sets -- all bounds-checked on
 the CPU, and every mixed and every reduced element recomputed in long double, before any of it runs on a GPU."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPU = os.path.join(ROOT, "tests", "cpu")
+import host_program
 
 
 def test_band_entry_points_are_clean_under_the_sanitizers(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "band_host")
-    srcs = [os.path.join(CPU, "band_host_main.cpp"), os.path.join(ROOT, "pythonic-disort_amd", "csrc", "rtd_api.hip"),
-            os.path.join(CPU, "host_asan_shadow.cpp")]
-    subprocess.run([gxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-static-libasan", "-static-libubsan", "-Wno-unused-result", "-I", os.path.join(CPU, "fake_hip"), "-x", "c++", *srcs,
-                    "-o", exe, "-ldl", "-lpthread"], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
-               FAKE_HIP_TOTAL=str(8 << 30))
-    for k in ("RTD_POOL_BYTES", "RTD_WORK_BYTES", "RTD_NO_PIPELINE", "RTD_RCCL_STUB"):
-        env.pop(k, None)
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
+    r = host_program.build_and_run(tmp_path, "band_host_main.cpp", "band_host")
     assert r.returncode == 0 and "BAND HOST OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
