@@ -2,11 +2,12 @@
 // workspace layout of an interface and the row-per-lane Gauss-Jordan step.  Included inside each file's anonymous namespace.
 #pragma once
 
-#define RTD_FENCE() asm volatile("" ::: "memory")
+#include "rtd_lane_util.h"  // RTD_FENCE, fast_rcp, static_for, readlane_f64
 #ifndef RTD_GJ_BATCH
 #define RTD_GJ_BATCH 3  /* cross-lane fetches in flight per batch - 1 (power of two minus one) */
 #endif
 
+// value of lane (lane ^ MASK): the ds_swizzle form of the boundary-condition kernels (the eigen kernels' is DPP: rtd_eig.hip)
 template <int MASK>
 __device__ __forceinline__ double xor_lane(double v) {
   static_assert(MASK < 32, "ds_swizzle stays inside a half of the wavefront");
@@ -37,27 +38,11 @@ __device__ __forceinline__ float group_max_key(float v) {
   return v;
 }
 
-__device__ __forceinline__ double fast_rcp(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  y = y * (2.0 - x * y);
-  y = y * (2.0 - x * y);
-  return y;
-}
-
 // value of `v` in lane `addr/4` (addr precomputed once per pivot step)
 __device__ __forceinline__ double bperm(int addr, double v) {
   const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(v));
   const int hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(v));
   return __hiloint2double(hi, lo);
-}
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
 }
 
 // value of lane K (compile-time) of this lane's 16-lane group: DPP row broadcast, VALU only

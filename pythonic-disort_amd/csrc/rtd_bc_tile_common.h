@@ -105,9 +105,6 @@ __device__ __forceinline__ v4f64 load_row_u(const double* ub, const unsigned kq8
   x[3] = ldg_u(ub, kq8, 96);
   return x;
 }
-__device__ __forceinline__ double readlane_f64(const double v, const int lane_uniform) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane_uniform), __builtin_amdgcn_readlane(__double2loint(v), lane_uniform));
-}
 
 // A chain whose result hangs on the last digits of its coefficients: the thermal (polynomial) particular solution of a layer with
 // a tiny eigenvalue k is ~ 1/k^(order + 1) times the source and is cancelled by the homogeneous part -- at k = 1.4e-3 (omega =

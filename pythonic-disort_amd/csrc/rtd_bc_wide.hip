@@ -41,10 +41,6 @@ using W = Ws<NP>;
 typedef const double __attribute__((address_space(4))) kdouble;
 __device__ __forceinline__ kdouble* as_k(const double* p) { return (kdouble*)(p); }
 
-__device__ __forceinline__ double readlane_f64(const double v, const int lane) {  // lane: wave-uniform
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
 // ------------------------------------------------------------------------------------------------
 // Interface operators: per (c, m, l < L-1) the transposes of Wp, Wq = (A^T Y' +- k Y^T A' / k') / 2 and rho_t, rho_b.
 // Two wavefronts (workgroups) per interface, 32 columns each, on the matrix cores: both products as v_mfma_f64_16x16x4_f64 chains

@@ -23,8 +23,7 @@
 
 namespace {
 
-// compiler-only barrier: keeps the scheduler from hoisting a whole unrolled loop's LDS loads
-#define RTD_FENCE() asm volatile("" ::: "memory")
+#include "rtd_lane_util.h"  // RTD_FENCE, fast_rcp, static_for
 
 // DPP control of a lane permutation "lane ^ MASK" inside a 16-lane row that one DPP move can express, else -1:
 // quad permutes for 1, 2, 3; row_half_mirror = ^7; row_ror:8 = ^8; row_mirror = ^15
@@ -34,7 +33,7 @@ constexpr __host__ __device__ int dpp_xor_ctrl(int mask) {
 
 template <int MASK>
 __device__ __forceinline__ double xor_lane(double v) {
-  // value of lane (lane ^ MASK)
+  // value of lane (lane ^ MASK): the DPP form of the eigen kernels (the boundary-condition kernels' is ds_swizzle: rtd_bc_common.h)
   // (lane ^ 16 and lane ^ 32 by v_permlane16_swap / v_permlane32_swap -- VALU, no LDS crossbar -- measured in round 4: the 64-stream
   //  eigen kernel 9.3 -> 9.5 ms per 128 cfg5 columns, the 128-stream one unchanged; not kept)
   if constexpr (MASK >= 32) return __shfl_xor(v, MASK, 64);  // across the halves of the wavefront: ds_bpermute (NP = 64 only)
@@ -79,18 +78,12 @@ constexpr __host__ __device__ int high_bit(int t) {
   return b;
 }
 
-// 1/sqrt(x) and 1/x to full double precision from the hardware seeds (x > 0, normal range)
+// 1/sqrt(x) to full double precision from the hardware seed (x > 0, normal range; 1/x: fast_rcp, rtd_lane_util.h)
 __device__ __forceinline__ double fast_rsqrt(double x) {
   double y = __builtin_amdgcn_rsq(x);
   const double hx = 0.5 * x;
   y = y * (1.5 - hx * y * y);
   y = y * (1.5 - hx * y * y);
-  return y;
-}
-__device__ __forceinline__ double fast_rcp(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  y = y * (2.0 - x * y);
-  y = y * (2.0 - x * y);
   return y;
 }
 // one Newton step from the ~5e-8 hardware seed: ~4e-15 relative (tools/hiptests/seed_accuracy.hip), enough for the
@@ -186,15 +179,6 @@ __device__ __forceinline__ double group_sum(double v) {
   if (NP > 16) v += xor_lane<16>(v);
   if (NP > 32) v += xor_lane<32>(v);
   return v;
-}
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
 }
 
 // value of lane K of this lane's NP-group, K a compile-time constant: a DPP row broadcast (VALU, no LDS crossbar)
@@ -804,6 +788,85 @@ struct FastPairStep<NP, NP - 1> {
                                              double&, double&, double&, double&) {}
 };
 
+// ---- stamps 5 -> 6 of the fused kernel: the one-sided Jacobi iteration on the columns of F.  In and out: w, one column per lane
+// (in: column j of F; out: a column of k Z).  where: NP ints of LDS (NP != 16: the columns' way back to their lanes); ecol: NP = 16,
+// the index of the eigen-column the lane holds afterwards; nsweep, converged: the sweeps made, and whether the last one found every
+// pair within the tolerance.
+template <int NP>
+__device__ __forceinline__ void jacobi_columns(double (&w)[NP], const int j, int* where, int& ecol, int& nsweep, bool& converged) {
+  constexpr int H = NP / 2;
+  const int u = j / H, p = j % H;  // lane (p, u): half u of the two columns of pair slot p
+  double xh[H], yh[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {  // columns p and p + H start in slot p: trade the halves with lane ^ H
+    if constexpr (NP == 16) {  // u is the lane's bit 3, two whole banks: merged in place by bank-masked moves, no select (dpp_merge)
+      xh[i] = dpp_merge<0x128, 0xC>(copy64(w[i]), w[H + i]);
+      yh[i] = dpp_merge<0x128, 0x3>(w[H + i], w[i]);
+    } else {
+      const double recv = xor_lane<H>(u ? w[i] : w[H + i]);
+      xh[i] = u ? recv : w[i];
+      yh[i] = u ? w[H + i] : recv;
+    }
+  }
+  int ix = p, iy = p + H;  // the columns' starting indices travel with them
+  for (int sweep = 0; sweep < 40; ++sweep) {
+    bool done;
+    double ax = 0.0, ay = 0.0;
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+      ax = fma(xh[i], xh[i], ax);
+      ay = fma(yh[i], yh[i], ay);
+    }
+    ax += xor_lane<H>(ax);
+    ay += xor_lane<H>(ay);
+    if constexpr (NP >= 32) {  // scaled rotations (FastPairStep)
+      int notconv = 0;
+      double sx = 1.0, sy = 1.0, rx = 1.0, ry = 1.0;
+      FastPairStep<NP, 0>::run(xh, yh, ax, ay, ix, iy, p, notconv, sx, sy, rx, ry);
+#pragma unroll
+      for (int i = 0; i < H; ++i) {  // the scales back into the columns
+        xh[i] *= sx;
+        yh[i] *= sy;
+      }
+      done = !__any(notconv);
+    } else {
+      unsigned long long notconv = 0;  // lanes that met a pair above the tolerance
+      PairStep<NP, 0>::run(xh, yh, ax, ay, ix, iy, p, notconv);
+      done = notconv == 0;
+    }
+    ++nsweep;
+    if (done) {
+      converged = true;
+      break;
+    }
+  }
+  // back to one column per lane: lane (p, 0) takes column X of its slot, lane (p, 1) column Y ...
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    if constexpr (NP == 16) {
+      w[i] = dpp_merge<0x128, 0xC>(copy64(xh[i]), yh[i]);
+      w[H + i] = dpp_merge<0x128, 0x3>(yh[i], xh[i]);
+    } else {
+      const double recv = xor_lane<H>(u ? xh[i] : yh[i]);
+      w[i] = u ? recv : xh[i];
+      w[H + i] = u ? yh[i] : recv;
+    }
+  }
+  if constexpr (NP == 16) {
+    // NP = 16: the column stays where the sweeps left it and stage 2 stores it under the index it carries -- nothing in between
+    // depends on which lane holds which eigen-column (its sums over them are transposed reductions); no 32 ds_bpermute here
+    ecol = u ? iy : ix;
+  } else {
+    // ... and every column returns to the lane it started in (its index j): the source lane of lane j through LDS
+    where[u ? iy : ix] = j;
+    __syncthreads();
+    const int src = where[j];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) w[i] = __shfl(w[i], src, NP);
+    __syncthreads();
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Fused eigen stage: assembly, Cholesky factors, one-sided Jacobi and the eigenvector /
 // particular-solution stage in ONE kernel per (c, m, l).  F, L, Qm and k Z never leave the CU (registers + LDS):
@@ -1201,83 +1264,9 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
   }
   }
   RTD_ESTAMP(5);
-  // one-sided Jacobi on the columns of F
   int nsweep = 0;
   bool converged = false;
-  {
-    constexpr int H = NP / 2;
-    const int u = j / H, p = j % H;  // lane (p, u): half u of the two columns of pair slot p
-    double xh[H], yh[H];
-#pragma unroll
-    for (int i = 0; i < H; ++i) {  // columns p and p + H start in slot p: trade the halves with lane ^ H
-      if constexpr (NP == 16) {  // u is the lane's bit 3, two whole banks: merged in place by bank-masked moves, no select (dpp_merge)
-        xh[i] = dpp_merge<0x128, 0xC>(copy64(w[i]), w[H + i]);
-        yh[i] = dpp_merge<0x128, 0x3>(w[H + i], w[i]);
-      } else {
-        const double recv = xor_lane<H>(u ? w[i] : w[H + i]);
-        xh[i] = u ? recv : w[i];
-        yh[i] = u ? w[H + i] : recv;
-      }
-    }
-    int ix = p, iy = p + H;  // the columns' starting indices travel with them
-    for (int sweep = 0; sweep < 40; ++sweep) {
-      bool done;
-      double ax = 0.0, ay = 0.0;
-#pragma unroll
-      for (int i = 0; i < H; ++i) {
-        ax = fma(xh[i], xh[i], ax);
-        ay = fma(yh[i], yh[i], ay);
-      }
-      ax += xor_lane<H>(ax);
-      ay += xor_lane<H>(ay);
-      if constexpr (NP >= 32) {  // scaled rotations (FastPairStep)
-        int notconv = 0;
-        double sx = 1.0, sy = 1.0, rx = 1.0, ry = 1.0;
-        FastPairStep<NP, 0>::run(xh, yh, ax, ay, ix, iy, p, notconv, sx, sy, rx, ry);
-#pragma unroll
-        for (int i = 0; i < H; ++i) {  // the scales back into the columns
-          xh[i] *= sx;
-          yh[i] *= sy;
-        }
-        done = !__any(notconv);
-      } else {
-        unsigned long long notconv = 0;  // lanes that met a pair above the tolerance
-        PairStep<NP, 0>::run(xh, yh, ax, ay, ix, iy, p, notconv);
-        done = notconv == 0;
-      }
-      ++nsweep;
-      if (done) {
-        converged = true;
-        break;
-      }
-    }
-    // back to one column per lane: lane (p, 0) takes column X of its slot, lane (p, 1) column Y ...
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-      if constexpr (NP == 16) {
-        w[i] = dpp_merge<0x128, 0xC>(copy64(xh[i]), yh[i]);
-        w[H + i] = dpp_merge<0x128, 0x3>(yh[i], xh[i]);
-      } else {
-        const double recv = xor_lane<H>(u ? xh[i] : yh[i]);
-        w[i] = u ? recv : xh[i];
-        w[H + i] = u ? yh[i] : recv;
-      }
-    }
-    if constexpr (NP == 16) {
-      // NP = 16: the column stays where the sweeps left it and stage 2 stores it under the index it carries -- nothing in between
-      // depends on which lane holds which eigen-column (its sums over them are transposed reductions); no 32 ds_bpermute here
-      ecol = u ? iy : ix;
-    } else {
-      // ... and every column returns to the lane it started in (its index j): the source lane of lane j through LDS
-      int* where = reinterpret_cast<int*>(sV[grp][0]);
-      where[u ? iy : ix] = j;
-      __syncthreads();
-      const int src = where[j];
-#pragma unroll
-      for (int i = 0; i < NP; ++i) w[i] = __shfl(w[i], src, NP);
-      __syncthreads();
-    }
-  }
+  jacobi_columns<NP>(w, j, reinterpret_cast<int*>(sV[grp][0]), ecol, nsweep, converged);  // one-sided Jacobi on the columns of F
   RTD_ESTAMP(6);
 #ifdef RTD_EIG_STAMPS
   est_sweeps = nsweep;

@@ -5,7 +5,10 @@ commit before the eigen kernel's select-free reductions and Cholesky steps).
 Shapes: the smallest that reach every path of the 16-stream-group eigen kernel -- 32 streams with 4 Fourier modes at 1, 5 and 20
 layers (four problems per wavefront: the last wavefront of a column is partial at 1 and 5), beam only, beam plus a thermal
 polynomial (mode 0 takes the thermal branch), no beam, one column whose 1/mu0 lies 5e-4 above an eigenvalue; 18 and 30 streams
-(padding streams inside the group of 16); one 16-stream and one 64-stream case for the neighbouring instances.
+(padding streams inside the group of 16); one 16-stream and one 64-stream case for the neighbouring instances.  Two cases pin the
+remaining instances of the fused eigen kernel (fixtures from the commit before that kernel was cut into stage functions): 66
+streams, the smallest count that takes the one-problem-per-wavefront instance, and the 32-stream beam + thermal case with the
+assembly on the matrix cores (RTD_EIG_MFMA=1, a switch the launcher reads once per process: computed in a fresh child process).
 
 What is pinned per case: ``Plan.tensors`` of every column (G from Y, A and k; K; B; the thermal vector G_inv_mu_inv; GC, which
 adds the boundary-condition solve) and u, u0 and the three fluxes at the interfaces and the layers' mid-points (E = exp(-k dtau)
@@ -13,6 +16,10 @@ and the thermal vectors dq, vb reach these).  An array over FULL_BYTES is stored
 (first Fourier mode of the first layer, last mode of the last layer) and every array, stored whole or not, with the SHA-256 of all its bytes.
 """
 import hashlib
+import os
+import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -32,7 +39,11 @@ CASES = {
     "q30_L3_padded": (30, 3, 2, "beam_thermal"),
     "q16_L3_neighbour": (16, 3, 2, "beam_thermal"),
     "q64_L3_neighbour": (64, 3, 1, "beam_thermal"),
+    "q66_L2_wide": (66, 2, 1, "beam_thermal"),
+    "q32_L5_beam_thermal_mfma": (32, 5, 2, "beam_thermal"),  # the inputs of q32_L5_beam_thermal
 }
+# cases computed under a run-time switch of the library that is read once per process: name -> environment of the child
+CHILD_ENV = {"q32_L5_beam_thermal_mfma": {"RTD_EIG_MFMA": "1"}}
 NFOURIER = 4
 RESONANCE_OFFSET = 5e-4  # 1/mu0 - k of the resonant column (column 1 of its case)
 
@@ -82,6 +93,17 @@ def compute(amd, cfg):
     return out
 
 
+def compute_in_child(name):
+    """``compute`` of a CHILD_ENV case in a fresh process that starts with the case's switches set."""
+    with tempfile.TemporaryDirectory(prefix="eigen_bits_") as tmp:
+        out = os.path.join(tmp, name + ".npz")
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), name, out], env=dict(os.environ, **CHILD_ENV[name]),
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        with np.load(out) as z:
+            return {k: z[k] for k in z.files}
+
+
 def digest(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
 
@@ -91,3 +113,11 @@ def stored_part(a):
     if a.nbytes <= FULL_BYTES or a.ndim < 3:
         return a
     return a[[0, a.shape[0] - 1], [0, a.shape[1] - 1]]
+
+
+if __name__ == "__main__":  # the child of compute_in_child: CASE OUTPUT.npz
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path[:0] = [os.path.dirname(here), os.path.join(os.path.dirname(here), "pythonic-disort_amd")]
+    import pydisort_amd
+    assert all(os.environ.get(k) == v for k, v in CHILD_ENV[sys.argv[1]].items())
+    np.savez(sys.argv[2], **compute(pydisort_amd, inputs(sys.argv[1])))

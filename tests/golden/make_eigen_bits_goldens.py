@@ -2,9 +2,10 @@
 """Writes tests/golden/eigen_bits/<case>.npz: the bit-exact eigen-stage tensors and evaluated fields of the cases of
 tests/eigen_bits_cases.py, as the library in the tree computes them on an MI355X.  Run it from a commit whose eigen stage is the
 one to pin (the fixtures in the tree: the commit before the select-free reductions and Cholesky steps), never to make a failing
-tests/test_gpu_eigen_stage_bits.py pass.
+tests/test_gpu_eigen_stage_bits.py pass.  (q66_L2_wide and q32_L5_beam_thermal_mfma: the commit before the fused eigen kernel was
+cut into stage functions.)
 
-Usage: python tests/golden/make_eigen_bits_goldens.py [OUTPUT_DIR]"""
+Usage: python tests/golden/make_eigen_bits_goldens.py [OUTPUT_DIR [CASE ...]]   (no CASE: every case)"""
 import os
 import sys
 
@@ -28,15 +29,17 @@ def resonant_mu0(amd, name):
     return 1.0 / (k + E.RESONANCE_OFFSET)
 
 
-def main(out_dir):
+def main(out_dir, only=()):
     import pydisort_amd as amd
     os.makedirs(out_dir, exist_ok=True)
     for name, (_, _, _, kind) in E.CASES.items():
+        if only and name not in only:
+            continue
         extra = {}
         if kind == "resonant":
             extra["resonant_mu0"] = np.float64(resonant_mu0(amd, name))
         cfg = E.inputs(name, **{k: float(v) for k, v in extra.items()})
-        got = E.compute(amd, cfg)
+        got = E.compute_in_child(name) if name in E.CHILD_ENV else E.compute(amd, cfg)
         if kind == "resonant":  # the column is what its name says
             K = np.abs(got["c1.K"][0, 0])
             assert np.min(np.abs(K - 1.0 / cfg["mu0"][1])) < 1e-3
@@ -53,4 +56,4 @@ def main(out_dir):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "eigen_bits"))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "eigen_bits"), sys.argv[2:])
