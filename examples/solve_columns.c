@@ -3,7 +3,8 @@
  * returned closures u / flux_up / flux_down, _assemble_intensity_and_fluxes.py:170-613).
  *
  *   ./solve_columns [ncols]      three-layer Henyey-Greenstein atmospheres, 16 streams, delta-M scaling, beam source;
- *                                prints flux_up, flux_down (diffuse, direct) at tau = 0 and u at one depth per column.
+ *                                prints flux_up, flux_down (diffuse, direct) at tau = 0 and u at one depth per column,
+ *                                then u at two viewing angles off the quadrature nodes (rtd_plan_set_view_mu, _fetch_view).
  *
  * What the host does: Gauss-Legendre nodes on [0, 1] (the reference's double-Gauss quadrature, pydisort.py:304) and the raw inputs.
  * What the device does: everything else (rtd_plan_set_columns_raw: delta-M scaling and source rescaling; rtd_plan_solve: eigen stage
@@ -93,7 +94,17 @@ int main(int argc, char** argv) {
   for (int c = 0; c < C; ++c)
     printf("column %d: flux_up(0) %.17g flux_down(0) %.17g + %.17g  u[mu_0, tau_1, phi_1] %.17g  u[-mu_0, tau_1, phi_0] %.17g\n", c,
            fup[c * ntau], fdn[c * ntau], fdir[c * ntau], u[((c * NQ + 0) * ntau + 1) * nphi + 1], u[((c * NQ + N) * ntau + 1) * nphi + 0]);
+  /* the same results at two viewing angles (up at mu = 0.8, down at mu = -0.6), interpolated in mu on the device from the u the
+   * plan holds: [C][nmu][ntau][nphi] */
+  const double view[2] = {0.8, -0.6};
+  double* u_mu = malloc(sizeof(double) * C * 2 * ntau * nphi);
+  CHECK(rtd_plan_set_view_mu(plan, 2, view, 0));
+  CHECK(rtd_plan_fetch_view(plan, u_mu, NULL));
+  for (int c = 0; c < C; ++c)
+    printf("view %d: u[mu = 0.8, tau_0, phi_0] %.17g  u[mu = -0.6, tau_1, phi_1] %.17g\n", c, u_mu[((c * 2 + 0) * ntau + 0) * nphi + 0],
+           u_mu[((c * 2 + 1) * ntau + 1) * nphi + 1]);
   CHECK(rtd_plan_destroy(plan));
   free(tau); free(omega); free(f); free(leg); free(mu0); free(I0); free(phi0); free(pts); free(u); free(fup); free(fdn); free(fdir);
+  free(u_mu);
   return 0;
 }

@@ -279,6 +279,8 @@ int rtd_plan_solve(rtd_plan* plan);
  * the values, argmax(tau <= tau_arr): at an interface tau = tau_arr[l] the result is the one-sided derivative from ABOVE, i.e.
  * of layer l, which ends there; at tau = 0 it is the right derivative.  Derivatives are generally discontinuous across
  * interfaces.  d(flux_down_direct)/d tau = -flux_down_direct / mu0.  Bits 0 and 2 together: RTD_ERR_ARG.
+ * Bit 3 (value 8) forms u on the device although the u pointer is NULL (nothing of it is copied): for rtd_plan_fetch_view behind
+ * the call.  rtd_plan_evaluate_band reads the same bit.
  * Any output pointer may be NULL.  Synchronous (returns when the host arrays are filled).
  * Returns RTD_ERR_TAU_RANGE if some tau lies outside its column (the reference raises ValueError). */
 int rtd_plan_evaluate(rtd_plan* plan, int32_t ntau, const double* tau, int32_t nphi, const double* phi,
@@ -381,6 +383,33 @@ int rtd_plan_fetch_actinic(rtd_plan* plan, double* act_up, double* act_down_diff
  * photolysis rate per level.  RTD_ERR_STATE without weights; a profile with a failed column is NaN and the call returns
  * RTD_ERR_NUMERIC, as rtd_plan_fetch_band. */
 int rtd_plan_fetch_band_actinic(rtd_plan* plan, double* act_up, double* act_down_diffuse, double* act_down_direct);
+/* Radiances at user polar angles: the reference's subroutines.interpolate (subroutines.py:614-705) -- barycentric polynomial
+ * interpolation in mu of the evaluated u and u0, each hemisphere on its own -- applied on the device to the results the plan holds
+ * (rtd_view_basis_kernel, rtd_view_apply_kernel).  It is polynomial interpolation of u as evaluated (with its Nakajima-Tanaka
+ * corrections when they are on), NOT an integration of the source function.  With x_j, j < N, the positive nodes and the rows of u
+ * ordered [x_0 .. x_{N-1}, -x_0 .. -x_{N-1}]: mu > 0 reads the rows 0 .. N-1, every other mu the rows N .. 2N-1 -- +0.0 and -0.0
+ * included (the reference's mask is `mu > 0`): mu = 0 is the DOWNWARD hemisphere's polynomial at its end.  With a = |mu|
+ *   l_j(a) = (b_j / (a - x_j)) / sum_k (b_k / (a - x_k)),  b_j = 1 / prod_{k != j} (x_j - x_k),  out = sum_j l_j u_row(j);
+ * a == x_j returns that row bit for bit.  b is formed on the host once per request in long double and rounded once; the sum is one
+ * chain, j ascending, without atomics: the bits depend on neither the launch geometry nor the window size.  The operator is linear
+ * and acts on mu alone, so it applies to whatever the result buffers hold: values, tau-antiderivatives or tau-derivatives, the
+ * partial sums of a mode shard (the shards' results add up).  A per-column relative azimuth needs nothing new: phi0[c].
+ * mu: [nmu], or [C][nmu] when per_column != 0, every |mu| <= 1 (else, or for a NaN or a null pointer, RTD_ERR_ARG); nmu <= 0
+ * withdraws the request.  RTD_ERR_STATE before rtd_plan_set_quadrature.  Sticky across solves and evaluations, like the band
+ * weights; the call itself touches the host only.  Under band weights per-column angles must be identical within a profile
+ * (RTD_ERR_ARG here when the weights are present, else from rtd_plan_fetch_band_view). */
+int rtd_plan_set_view_mu(rtd_plan* plan, int32_t nmu, const double* mu, int32_t per_column);
+/* u_mu [C][nmu][ntau][nphi], u0_mu [C][nmu][ntau] of the LATEST evaluation (run, run_fetch, evaluate, evaluate_band), interpolated
+ * on the plan's stream and copied out; either pointer may be NULL.  RTD_ERR_STATE when no angles are set, when the plan holds no
+ * evaluated results (as rtd_plan_fetch_actinic), or when u_mu is asked for but the latest evaluation formed no u (nphi = 0, or an
+ * evaluation whose u pointer was NULL without bit 3 of its flag word); RTD_ERR_NUMERIC as rtd_plan_fetch reports it: any mode for
+ * u_mu, mode 0 for u0_mu.  The buffers behind these calls are allocated at the first of them: a plan that never asks holds what it
+ * held before.  The gathered-results collectives (rtd_comm_*) do not carry these arrays. */
+int rtd_plan_fetch_view(rtd_plan* plan, double* u_mu, double* u0_mu);
+/* The same summed over the spectral points with every weight set (rtd_band_reduce_kernel; masks: any mode for u_mu, mode 0 for
+ * u0_mu): u_mu [P][K][nmu][ntau][nphi], u0_mu [P][K][nmu][ntau].  RTD_ERR_STATE without weights; a profile with a failed column
+ * is NaN and the call returns RTD_ERR_NUMERIC, as rtd_plan_fetch_band. */
+int rtd_plan_fetch_band_view(rtd_plan* plan, double* u_mu, double* u0_mu);
 /* device pointers of the result buffers of rtd_plan_run (for a device-side collective); any pointer may be NULL */
 int rtd_plan_result_dev_ptrs(rtd_plan* plan, void** u_dev, int64_t* u_bytes, void** flux_dev, int64_t* flux_bytes);
 

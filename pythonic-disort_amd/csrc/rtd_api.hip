@@ -327,6 +327,15 @@ struct rtd_plan {
   static constexpr int RES_NONE = 2;
   int res_order = RES_NONE;
   DevBuf ev_act, rb_act;
+  // radiances at user polar angles (rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view).  The request lives on the
+  // host until a fetch: view_mu_h is the caller's list [nmu] or [C][nmu], h_mu_pos the plan's positive nodes (set_quadrature), and
+  // view_stale says that the device's copy of the angles, the barycentric weights view_b [N] and the basis view_l [C or 1][nmu][N]
+  // with its flags view_flag (ints) do not match them.  res_has_u: the latest evaluation formed u (it had azimuths and wanted u).
+  // Every buffer below is grown at the first fetch: a plan that never asks holds nothing more.
+  int view_nmu = 0;
+  bool view_per_column = false, view_stale = true, res_has_u = false;
+  std::vector<double> view_mu_h, h_mu_pos;
+  DevBuf view_mu, view_b, view_l, view_flag, ev_view_u, ev_view_u0, rb_view_u, rb_view_u0;
   // export buffers
   double* ex_buf = nullptr;
   // Nakajima-Tanaka corrections (optional)
@@ -775,7 +784,7 @@ extern "C" {
 
 int rtd_comm_destroy(rtd_plan* p);
 
-int rtd_version(void) { return 215; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt
+int rtd_version(void) { return 216; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt; 216: rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view, bit 3 of the evaluation flag word
 
 const char* rtd_last_error(void) { return g_err.c_str(); }
 
@@ -1090,6 +1099,8 @@ int rtd_plan_set_quadrature(rtd_plan* p, const double* mu_pos, const double* wei
   for (const auto& row : rows) std::memcpy(img.data() + (reinterpret_cast<const char*>(row.dev) - base), row.host->data(), nb);
   HIP_TRY(hipMemcpyAsync((void*)p->d.mu, img.data(), span, hipMemcpyHostToDevice, p->stream));
   p->quad_pending = true;  // (no wait: the image stays with the plan)
+  p->h_mu_pos.assign(mu_pos, mu_pos + N);  // (the barycentric weights of rtd_plan_fetch_view are formed from these, on the host)
+  p->view_stale = true;
   p->new_quadrature();
   return 0;
 }
@@ -1573,6 +1584,65 @@ __global__ void rtd_actinic_kernel(RtdDev d, const double* ev_tau, const double*
   act[2 * CT + idx] = D;
 }
 
+// Radiances at user polar angles: the reference's subroutines.interpolate (subroutines.py:614-705), barycentric polynomial
+// interpolation in mu of the results the plan holds, each hemisphere on its own, for every column, angle and point at once.  The
+// operator is LINEAR in the rows of u / u0 and does not touch tau or phi, so it commutes with everything the result buffers may
+// hold: values, tau-antiderivatives or tau-derivatives (res_order), u with its Nakajima-Tanaka corrections, the partial sums of a
+// mode shard (the shards' interpolants add up to the interpolant of the sum).  It is polynomial interpolation of the evaluated u,
+// not an integration of the source function.
+//
+// Basis.  x_j, j < N, the positive nodes; the rows of u are [x_0 .. x_{N-1}, -x_0 .. -x_{N-1}].  mu > 0 reads the rows 0 .. N-1,
+// every other mu -- +0.0 and -0.0 included, the reference's mask is `mu > 0` -- the rows N .. 2N-1.  With a = |mu| the basis is the
+// same for both (the sign of the negated nodes cancels in the quotient):
+//   l_j(a) = (b_j / (a - x_j)) / sum_k (b_k / (a - x_k)),   b_j = 1 / prod_{k != j} (x_j - x_k)
+// b comes from the host (view_weights: long double, rounded once, scaled by the largest magnitude -- only ratios matter).  If
+// a == x_j the basis is the unit vector e_j and the flag carries j: the apply kernel then COPIES row j, bit for bit, as the
+// reference assigns yi[j].  One thread per (column, angle); n = C nmu, or nmu for a list shared by the columns.
+//   flag = hemisphere (bit 0: 1 = the rows N .. 2N-1) | (j + 1) << 8 at a node
+__global__ void rtd_view_basis_kernel(const double* mu, long n, const double* x, const double* b, int N, double* l, int* flag) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const double m = mu[idx], a = fabs(m);
+  double* lj = l + idx * N;
+  int hit = -1;
+  for (int j = 0; j < N; ++j)
+    if (a == x[j]) hit = j;
+  if (hit >= 0) {
+    for (int j = 0; j < N; ++j) lj[j] = j == hit ? 1.0 : 0.0;
+  } else {
+    double s = 0.0;
+    for (int j = 0; j < N; ++j) {
+      const double t = b[j] / (a - x[j]);
+      lj[j] = t;
+      s += t;
+    }
+    for (int j = 0; j < N; ++j) lj[j] /= s;
+  }
+  flag[idx] = (m > 0.0 ? 0 : 1) | ((hit + 1) << 8);
+}
+
+// out [C][nmu][E] = sum_j l[c][m][j] X[c][h N + j][E], X = ev_u (E = ntau nphi) or ev_u0 (E = ntau).  One thread per output
+// element, e fastest across the lanes: for each j a wavefront reads runs of consecutive doubles.  The sum is one chain, j ascending,
+// no atomics, no cross-lane reduction: the bits depend on the inputs alone, not on the launch geometry or the window size.
+// lstride / fstride: doubles / ints from one column's basis and flags to the next, 0 for a shared list.
+__global__ void rtd_view_apply_kernel(const double* l, long lstride, const int* flag, long fstride, const double* X, int N, int nmu,
+                                      long E, long C, double* out) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= C * nmu * E) return;
+  const long e = idx % E, cm = idx / E, c = cm / nmu;
+  const int m = (int)(cm % nmu), f = flag[c * fstride + m];
+  const double* x = X + (c * 2 * N + ((f & 1) ? N : 0)) * E + e;
+  const double* lj = l + c * lstride + (long)m * N;
+  double acc;
+  if (f >> 8) {
+    acc = x[(long)((f >> 8) - 1) * E];
+  } else {
+    acc = lj[0] * x[0];
+    for (int j = 1; j < N; ++j) acc += lj[j] * x[(long)j * E];
+  }
+  out[idx] = acc;
+}
+
 }  // namespace
 
 int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wvnmlo, const double* wvnmhi, double* out) {
@@ -1934,6 +2004,7 @@ int rtd_plan_run(rtd_plan* p) {
   RtdEval e = make_eval(p, p->eval_order, true);
   int rc = launch_solve(p, true, &e, p->have_nt);
   p->res_order = rc ? rtd_plan::RES_NONE : p->eval_order;
+  p->res_has_u = e.u != nullptr;
   return rc;
 }
 
@@ -2034,6 +2105,7 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
   for (int w = std::max(0, p->nwin - 2); w < p->nwin; ++w)
     if ((rc = drain(w))) return rc;
   p->res_order = p->eval_order;
+  p->res_has_u = e.u != nullptr;
   return check_status(p, u != nullptr);
 }
 
@@ -2065,6 +2137,7 @@ static int evaluate_queued(rtd_plan* p, int32_t ntau, const double* tau, int32_t
   if (rc) return rc;
   if (p->pipelined && !solve_again) p->fork_needed = true;  // the next solve's eigen stream must not overwrite what this pass still reads
   p->res_order = order;
+  p->res_has_u = e.u != nullptr;
   return 0;
 }
 
@@ -2072,7 +2145,7 @@ int rtd_plan_evaluate(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi
                       int32_t antiderivative, double* u, double* u0, double* flux_up, double* fdn, double* fdir,
                       double* ulast) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
-  int rc = evaluate_queued(p, ntau, tau, nphi, phi, antiderivative, u != nullptr);
+  int rc = evaluate_queued(p, ntau, tau, nphi, phi, antiderivative, u != nullptr || (antiderivative & 8) != 0);
   if (rc) return rc;
   if (ulast) {  // queued before the fetch, whose status check drains the stream: a numerical failure of SOME columns must not
     //             leave the healthy columns' ulast unwritten (numeric_errors = "nan" keeps them)
@@ -2143,7 +2216,7 @@ int rtd_plan_evaluate_band(rtd_plan* p, int32_t ntau, const double* tau, int32_t
                            double* u0, double* flux_up, double* fdn, double* fdir) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
   if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede evaluate_band");
-  int rc = evaluate_queued(p, ntau, tau, nphi, phi, flags, u != nullptr);
+  int rc = evaluate_queued(p, ntau, tau, nphi, phi, flags, u != nullptr || (flags & 8) != 0);
   if (rc) return rc;
   return drained(p, band_fetch_queued(p, u, u0, flux_up, fdn, fdir));
 }
@@ -2197,6 +2270,150 @@ int rtd_plan_fetch_band_actinic(rtd_plan* p, double* act_up, double* act_down_di
   if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede fetch_band_actinic");
   if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
   return drained(p, band_actinic_fetch_queued(p, act_up, act_down_diffuse, act_down_direct));
+}
+
+// the barycentric weights b_j = 1 / prod_{k != j} (x_j - x_k) of the plan's positive nodes: long double, k ascending, scaled by
+// the largest magnitude and rounded once (64 nodes: about 38 decades between the smallest and the largest, which float64 holds)
+static std::vector<double> view_weights(const std::vector<double>& x) {
+  const size_t N = x.size();
+  std::vector<long double> b(N);
+  long double big = 0.0L;
+  for (size_t j = 0; j < N; ++j) {
+    long double prod = 1.0L;
+    for (size_t k = 0; k < N; ++k)
+      if (k != j) prod *= (long double)x[j] - (long double)x[k];
+    b[j] = 1.0L / prod;
+    big = std::max(big, std::fabs(b[j]));
+  }
+  std::vector<double> out(N);
+  for (size_t j = 0; j < N; ++j) out[j] = (double)(b[j] / big);
+  return out;
+}
+
+// per-column angles under band weights: the G columns of a profile must carry identical angles (their interpolants are summed)
+static bool view_band_consistent(const rtd_plan* p) {
+  if (!p->view_per_column || p->view_nmu <= 0 || p->band_G <= 1) return true;
+  const int64_t G = p->band_G, nmu = p->view_nmu;
+  for (int64_t c = 0; c < p->d.C; ++c)
+    if (c % G != 0 && std::memcmp(&p->view_mu_h[c * nmu], &p->view_mu_h[(c - c % G) * nmu], (size_t)nmu * 8) != 0) return false;
+  return true;
+}
+
+int rtd_plan_set_view_mu(rtd_plan* p, int32_t nmu, const double* mu, int32_t per_column) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (nmu <= 0) {  // withdraw the request (the buffers, if any, stay with the plan)
+    p->view_nmu = 0;
+    p->view_mu_h.clear();
+    p->view_stale = true;
+    return 0;
+  }
+  if (!mu) return fail(RTD_ERR_ARG, "set_view_mu: null angles");
+  if (!p->have_quad) return fail(RTD_ERR_STATE, "set_quadrature must precede set_view_mu");
+  const int64_t n = (per_column ? (int64_t)p->d.C : 1) * nmu;
+  for (int64_t i = 0; i < n; ++i)
+    if (!(std::fabs(mu[i]) <= 1.0)) return fail(RTD_ERR_ARG, "mu values must be between -1 and 1");
+  std::vector<double> keep(mu, mu + n);
+  std::swap(keep, p->view_mu_h);
+  const int old_nmu = p->view_nmu;
+  const bool old_pc = p->view_per_column;
+  p->view_nmu = nmu;
+  p->view_per_column = per_column != 0;
+  if (!view_band_consistent(p)) {  // refused: the earlier request stands
+    std::swap(keep, p->view_mu_h);
+    p->view_nmu = old_nmu;
+    p->view_per_column = old_pc;
+    return fail(RTD_ERR_ARG, "set_view_mu: the columns of a band profile must carry identical angles");
+  }
+  p->view_stale = true;
+  return 0;
+}
+
+// the basis of the requested angles (when stale) and the interpolation of the resident results into ev_view_u / ev_view_u0, on the
+// plan's stream.  Every fetch drains the stream before it returns, so no copy reads view_mu_h when set_view_mu next replaces it.
+static int view_queued(rtd_plan* p, bool want_u, bool want_u0) {
+  HIP_TRY(hipSetDevice(p->device));
+  const ResultShape r(p);
+  const int64_t N = p->d.N, nmu = p->view_nmu, rows = p->view_per_column ? r.C : 1, n = rows * nmu;
+  int rc;
+  int* flag = nullptr;
+  (void)hipGetLastError();
+  if (p->view_stale) {
+    if ((rc = grow(p, p->view_mu, n)) || (rc = grow(p, p->view_b, N)) || (rc = grow(p, p->view_l, n * N)) ||
+        (rc = grow(p, p->view_flag, (n + 1) / 2 + 1)))
+      return rc;
+    const std::vector<double> b = view_weights(p->h_mu_pos);
+    HIP_TRY(hipMemcpyAsync(p->view_mu, p->view_mu_h.data(), (size_t)n * 8, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->view_b, b.data(), (size_t)N * 8, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));  // (b is a local; the basis is formed once per request, not per fetch)
+    flag = reinterpret_cast<int*>(p->view_flag.p);
+    hipLaunchKernelGGL(rtd_view_basis_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p->stream, (const double*)p->view_mu, (long)n,
+                       (const double*)p->d.mu, (const double*)p->view_b, (int)N, p->view_l.p, flag);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_view_basis_kernel: ") + hipGetErrorString(e));
+    p->view_stale = false;
+  }
+  flag = reinterpret_cast<int*>(p->view_flag.p);
+  const long ls = p->view_per_column ? (long)(nmu * N) : 0, fs = p->view_per_column ? (long)nmu : 0;
+  struct Pass { bool on; const double* X; int64_t E; DevBuf* out; } pass[2] = {{want_u, p->ev_u, r.nt * r.np, &p->ev_view_u},
+                                                                              {want_u0, p->ev_u0, r.nt, &p->ev_view_u0}};
+  for (const Pass& q : pass) {
+    if (!q.on) continue;
+    const int64_t total = r.C * nmu * q.E;
+    if ((rc = grow(p, *q.out, total))) return rc;
+    hipLaunchKernelGGL(rtd_view_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, (const double*)p->view_l, ls,
+                       (const int*)flag, fs, q.X, (int)N, (int)nmu, (long)q.E, (long)r.C, q.out->p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_view_apply_kernel: ") + hipGetErrorString(e));
+  }
+  return 0;
+}
+
+// what rtd_plan_fetch_view and rtd_plan_fetch_band_view refuse alike
+static int view_refused(rtd_plan* p, const double* u_mu) {
+  if (p->view_nmu <= 0) return fail(RTD_ERR_STATE, "set_view_mu must precede fetch_view");
+  if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
+  if (u_mu && !p->res_has_u) return fail(RTD_ERR_STATE, "fetch_view: the latest evaluation formed no u (no azimuths, or u was not wanted)");
+  return 0;
+}
+
+static int view_fetch_queued(rtd_plan* p, double* u_mu, double* u0_mu) {
+  int rc = view_queued(p, u_mu != nullptr, u0_mu != nullptr);
+  if (rc) return rc;
+  const ResultShape r(p);
+  const int64_t nmu = p->view_nmu;
+  if (u_mu) HIP_TRY(hipMemcpyAsync(u_mu, p->ev_view_u, (size_t)(r.C * nmu * r.nt * r.np) * 8, hipMemcpyDeviceToHost, p->stream));
+  if (u0_mu) HIP_TRY(hipMemcpyAsync(u0_mu, p->ev_view_u0, (size_t)(r.C * nmu * r.nt) * 8, hipMemcpyDeviceToHost, p->stream));
+  return check_status(p, u_mu != nullptr);  // (u0 comes from Fourier mode 0 alone)
+}
+
+static int band_view_fetch_queued(rtd_plan* p, double* u_mu, double* u0_mu) {
+  int rc = view_queued(p, u_mu != nullptr, u0_mu != nullptr);
+  if (rc) return rc;
+  const ResultShape r(p);
+  const int64_t PK = (int64_t)(r.C / p->band_G) * p->band_K, Eu = p->view_nmu * r.nt * r.np, Eu0 = p->view_nmu * r.nt;
+  if (u_mu && (rc = grow(p, p->rb_view_u, PK * Eu))) return rc;
+  if (u0_mu && (rc = grow(p, p->rb_view_u0, PK * Eu0))) return rc;
+  hipError_t e = hipSuccess;
+  if (u_mu) e = band_reduce(p, p->ev_view_u, 0xFFFF, Eu, p->rb_view_u, u_mu);
+  if (e == hipSuccess && u0_mu) e = band_reduce(p, p->ev_view_u0, 0xFF, Eu0, p->rb_view_u0, u0_mu);
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("fetch_band_view: ") + hipGetErrorString(e));
+  return check_status(p, u_mu != nullptr);
+}
+
+int rtd_plan_fetch_view(rtd_plan* p, double* u_mu, double* u0_mu) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  int rc = view_refused(p, u_mu);
+  if (rc) return rc;
+  return drained(p, view_fetch_queued(p, u_mu, u0_mu));
+}
+
+int rtd_plan_fetch_band_view(rtd_plan* p, double* u_mu, double* u0_mu) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede fetch_band_view");
+  int rc = view_refused(p, u_mu);
+  if (rc) return rc;
+  if (!view_band_consistent(p)) return fail(RTD_ERR_ARG, "fetch_band_view: the columns of a band profile must carry identical angles");
+  return drained(p, band_view_fetch_queued(p, u_mu, u0_mu));
 }
 
 int rtd_plan_set_nt(rtd_plan* p, int32_t nleg_all, const double* weighted_leg_all, const double* f_arr,

@@ -11,6 +11,17 @@ def _f64(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
 
 
+def view_angles(mu, rows, axis="C"):
+    """The polar-angle cosines of ``Plan.set_view`` checked on the host: [nmu] or [rows, nmu], every |mu| <= 1 (the reference's
+    ``interpolate`` raises the same text) -> C-contiguous float64."""
+    mu = _f64(np.atleast_1d(np.asarray(mu, dtype=np.float64)))
+    if mu.ndim not in (1, 2) or mu.shape[-1] < 1 or (mu.ndim == 2 and mu.shape[0] != rows):
+        raise ValueError(f"mu must have the shape [nmu] or [{axis} = {rows}, nmu] with nmu >= 1.")
+    if not np.all(np.abs(mu) <= 1):
+        raise ValueError("mu values must be between -1 and 1.")
+    return mu
+
+
 class Plan:
     def __init__(self, prep, device=0, work_columns=0, retain_bytes=0, retain_form=0):
         """prep: dict from _prepare.prepare_columns.  work_columns: columns whose intermediates are resident at a time
@@ -252,7 +263,8 @@ class Plan:
     def evaluate_band(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
         """``evaluate`` without copying the unreduced fields out: tau [C, ntau] (the t-th point of each of a profile's columns must
         be the same physical level), phi [nphi] or None -> the dict of ``fetch_band`` (include/rtd.h: rtd_plan_evaluate_band);
-        "act" in `want` adds the reduced actinic fluxes of ``fetch_band_actinic``."""
+        "act" in `want` adds the reduced actinic fluxes of ``fetch_band_actinic``, "view" the reduced radiances at the angles of
+        ``set_view`` (``fetch_band_view``; "view_u" / "view_u0": one of the two)."""
         if antiderivative and derivative:
             raise ValueError("antiderivative and derivative exclude each other.")
         tau = _f64(np.atleast_2d(tau))
@@ -262,11 +274,16 @@ class Plan:
         nphi = 0 if phi is None else len(phi)
         out = self._band_arrays(ntau, nphi, want)
         self._ev_shape = (ntau, nphi)
+        view = self._view_want(want)
+        keep_u = 8 if ("u" in view and nphi > 0) else 0  # (u is formed on the device although nothing of it is copied)
         self._checked_band(self._lib.rtd_plan_evaluate_band(
-            self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi), int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0),
+            self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi),
+            int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0) | keep_u,
             *[_lib.dptr(out[k]) for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")]))
         if "act" in want:
             out.update(self.fetch_band_actinic())
+        if view:
+            out.update(self.fetch_band_view(view))
         return out
 
     _ACT = ("flux_act_up", "flux_act_down_diffuse", "flux_act_down_direct")
@@ -309,6 +326,81 @@ class Plan:
         out = {k: np.empty((P, K, self._resident_ntau())) for k in self._ACT}
         self._checked_band(self._lib.rtd_plan_fetch_band_actinic(self._h, *[_lib.dptr(out[k]) for k in self._ACT]))
         return out
+
+    _VIEW = ("u_mu", "u0_mu")
+
+    def set_view(self, mu):
+        """Polar-angle cosines at which ``fetch_view`` / ``fetch_band_view`` (and "view" in the `want` of ``evaluate`` /
+        ``evaluate_band``) return the radiances: mu [nmu] shared by the columns, or [C, nmu]; None withdraws the request
+        (include/rtd.h: rtd_plan_set_view_mu).  mu > 0 is interpolated among the upward rows of u, every other mu -- 0 included --
+        among the downward rows, as the reference's ``subroutines.interpolate`` does.  Sticky across solves and evaluations.
+        Under band weights, angles given per column must be the same for the columns of a profile."""
+        if mu is None:
+            _lib.check(self._lib.rtd_plan_set_view_mu(self._h, 0, None, 0))
+            self._view = None
+            return
+        mu = view_angles(mu, self.C)
+        band = getattr(self, "_band", None)
+        if mu.ndim == 2 and band is not None:
+            per_profile = mu.reshape(band[0], self.C // band[0], -1)
+            if not np.array_equal(per_profile, np.broadcast_to(per_profile[:, :1], per_profile.shape)):
+                raise ValueError("mu must be the same for the columns of a band profile.")
+        _lib.check(self._lib.rtd_plan_set_view_mu(self._h, mu.shape[-1], _lib.dptr(mu), int(mu.ndim == 2)))
+        self._view = mu.shape[-1]
+
+    def _resident_shape(self):
+        """(ntau, nphi) of the results the plan holds now, as the plan itself reports them (``_resident_ntau``; u_bytes =
+        C Q ntau nphi 8)."""
+        ub, fb = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.rtd_plan_result_dev_ptrs(self._h, None, C.byref(ub), None, C.byref(fb)))
+        ntau = int(fb.value // (24 * self.C))
+        return ntau, (int(ub.value // (8 * self.C * self.Q * ntau)) if ntau > 0 else 0)
+
+    def _view_arrays(self, lead, want, out):
+        """The host arrays of the two view fetches: `lead` + (nmu, ntau[, nphi]).  u_mu is None when "u" is not wanted or the
+        resident results have no azimuths; arrays of `out` are checked and filled in place, the others allocated."""
+        if getattr(self, "_view", None) is None:
+            raise ValueError("set_view must precede fetch_view / fetch_band_view.")
+        ntau, nphi = self._resident_shape()
+        shapes = {}
+        if "u" in want and nphi > 0:
+            shapes["u_mu"] = lead + (self._view, ntau, nphi)
+        if "u0" in want:
+            shapes["u0_mu"] = lead + (self._view, ntau)
+        given = out or {}
+        arrays = dict(u_mu=None, u0_mu=None)
+        for k, shape in shapes.items():
+            a = given.get(k)
+            if a is None:
+                a = np.empty(shape)
+            elif not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable and a.shape == shape):
+                raise ValueError(f"out[{k!r}] must be a writeable C-contiguous float64 array of the shape {shape}.")
+            arrays[k] = a
+        return arrays
+
+    def fetch_view(self, want=("u", "u0"), out=None):
+        """Radiances at the angles of ``set_view`` of the results the plan holds -- after run(), run_fetch(), evaluate() or
+        evaluate_band(), at the points and in the order (value, antiderivative, derivative) of the latest of them -- interpolated
+        on the device from the resident u and u0 (include/rtd.h: rtd_plan_fetch_view) -> dict(u_mu [C, nmu, ntau, nphi],
+        u0_mu [C, nmu, ntau]); what `want` leaves out is None, and so is u_mu when the results have no azimuths.  `out`: dict whose
+        arrays of those names are filled in place (C-contiguous float64 of those shapes, anything else is a ValueError)."""
+        arrays = self._view_arrays((self.C,), want, out)
+        self._checked(self._lib.rtd_plan_fetch_view(self._h, _lib.dptr(arrays["u_mu"]), _lib.dptr(arrays["u0_mu"])), arrays)
+        return arrays
+
+    def fetch_band_view(self, want=("u", "u0")):
+        """``fetch_view`` summed over the spectral points with every weight set on the device (include/rtd.h:
+        rtd_plan_fetch_band_view) -> dict(u_mu [P, K, nmu, ntau, nphi], u0_mu [P, K, nmu, ntau])."""
+        if getattr(self, "_band", None) is None:
+            raise ValueError("set_band_weights must precede fetch_band_view.")
+        arrays = self._view_arrays(tuple(self._band), want, None)
+        self._checked_band(self._lib.rtd_plan_fetch_band_view(self._h, _lib.dptr(arrays["u_mu"]), _lib.dptr(arrays["u0_mu"])))
+        return arrays
+
+    @staticmethod
+    def _view_want(want):
+        """"view" in `want` asks for both u_mu and u0_mu, "view_u" / "view_u0" for one -> the `want` of the view fetches."""
+        return tuple(k for k, names in (("u", ("view", "view_u")), ("u0", ("view", "view_u0"))) if any(n in want for n in names))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -409,7 +501,9 @@ class Plan:
     def evaluate(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
         """tau [C, ntau]; phi [nphi] or None -> dict of arrays (u [C,Q,ntau,nphi], u0 [C,Q,ntau],
         flux_up / flux_down_diffuse / flux_down_direct [C,ntau], ulast [C,Q,ntau]; "act" in `want` adds the actinic fluxes of
-        ``fetch_actinic`` at the same points, in the same order).  derivative: every output is its
+        ``fetch_actinic`` at the same points, in the same order, "view" the radiances u_mu [C,nmu,ntau,nphi] and u0_mu [C,nmu,ntau]
+        of ``fetch_view`` at the angles of ``set_view`` -- "view_u" / "view_u0": one of the two; u itself then stays on the device
+        unless "u" is wanted too).  derivative: every output is its
         derivative with respect to the unscaled tau (include/rtd.h: bit 2 of rtd_plan_evaluate's flag word; one-sided from above
         at an interface); not together with antiderivative."""
         if antiderivative and derivative:
@@ -425,14 +519,18 @@ class Plan:
         ul = np.empty((self.C, self.Q, ntau)) if "ulast" in want else None
         fl = [np.empty((self.C, ntau)) for _ in range(3)] if "flux" in want else [None] * 3
         out.update(u=u, u0=u0, ulast=ul, flux_up=fl[0], flux_down_diffuse=fl[1], flux_down_direct=fl[2])
+        view = self._view_want(want)
+        keep_u = 8 if ("u" in view and nphi > 0) else 0  # (u is formed on the device although nothing of it is copied)
         self._checked(self._lib.rtd_plan_evaluate(self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi),
-                                                  int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0),
+                                                  int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0) | keep_u,
                                                   _lib.dptr(u),
                                                   _lib.dptr(u0),
                                                   _lib.dptr(fl[0]), _lib.dptr(fl[1]), _lib.dptr(fl[2]),
                                                   _lib.dptr(ul)), out)
         if "act" in want:
             out.update(self.fetch_actinic())
+        if view:
+            out.update(self.fetch_view(view))
         return out
 
     # ---- throughput form (results stay in HBM until fetch) ----
@@ -624,7 +722,7 @@ class Plan:
             st = self.column_status()
             for k, a in arrays.items():
                 if a is not None:
-                    a[(st & (0xFFFF if k in ("u", "ulast") else 0xFF)) != 0] = np.nan
+                    a[(st & (0xFFFF if k in ("u", "ulast", "u_mu") else 0xFF)) != 0] = np.nan
             return
         _lib.check(rc)
 

@@ -70,7 +70,10 @@ SIGNATURES = {
     "rtd_plan_evaluate_band": (C.c_int, [_vp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32] + [_dp] * 5),
     "rtd_plan_fetch_actinic": (C.c_int, [_vp] + [_dp] * 3),
     "rtd_plan_fetch_band_actinic": (C.c_int, [_vp] + [_dp] * 3),
-    "rtd_plan_set_bdrf_samples": (C.c_int, [_vp, C.c_int32, _dp, _dp]),
+    "rtd_plan_set_view_mu": (C.c_int, [_vp, C.c_int32, _dp, C.c_int32]),
+    "rtd_plan_fetch_view": (C.c_int, [_vp, _dp, _dp]),
+    "rtd_plan_fetch_band_view": (C.c_int, [_vp, _dp, _dp]),
+    "rtd_plan_set_bdrf_samples":(C.c_int, [_vp, C.c_int32, _dp, _dp]),
     "rtd_plan_set_mode_shard": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "rtd_plan_invalidate_tables": (C.c_int, [_vp]),
     "rtd_plan_solve": (C.c_int, [_vp]),

@@ -8,7 +8,7 @@ Legendre moments of the P G columns (include/rtd.h: rtd_plan_set_columns_band) a
 weights (rtd_plan_set_band_weights).  Column p G + g throughout."""
 import numpy as np
 
-from ._engine import Plan
+from ._engine import Plan, view_angles
 from ._prepare import double_gauss
 from .batch import BatchSolution, _nt_checks, _retention, _thermal_inputs
 
@@ -206,6 +206,21 @@ class BandSolution:
         r = self._eval(levels, None, ("act",))
         return self._out(r["flux_act_up"] + r["flux_act_down_diffuse"] + r["flux_act_down_direct"])
 
+    def _set_view(self, mu):
+        mu = view_angles(mu, self.P, "P")
+        self.plan.set_view(np.repeat(mu, self.G, axis=0) if mu.ndim == 2 else mu)
+
+    def u_at(self, mu, levels, phi):
+        """Band radiance at the polar-angle cosines mu [nmu] or [P, nmu] -> [P, K, nmu, nlev, nphi]: every column's u is
+        interpolated in mu on the device (``BatchSolution.u_at``), then summed over the spectral points."""
+        self._set_view(mu)
+        return self._out(self._eval(levels, phi, ("view_u",))["u_mu"])
+
+    def u0_at(self, mu, levels=None):
+        """-> [P, K, nmu, nlev] (``u_at``)"""
+        self._set_view(mu)
+        return self._out(self._eval(levels, None, ("view_u0",))["u0_mu"])
+
     def net_flux_convergence(self):
         """-> [P, K, L]: F_net[l] - F_net[l + 1], F_net = down_diffuse + down_direct - up: the layers' absorbed power (host
         arithmetic on the reduced level fluxes)."""
@@ -258,7 +273,7 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
 
 def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, levels=None, phi=None,
                         chunk_columns=0, NLeg=None, NFourier=None, delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None,
-                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False, NT_cor=False):
+                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False, mu=None, NT_cor=False):
     """Throughput form of ``pydisort_band`` (as ``solve_columns_streamed`` is of ``pydisort_batch``): ONE plan holds the inputs
     and the results of all P G columns, the intermediates of the solve live for `chunk_columns` columns at a time, the results at
     `levels` (None: all L + 1) and `phi` are reduced on the device and only the P band results travel to the host -- 1 / G of what
@@ -266,7 +281,11 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
     Returns dict(u [P, K, NQuad, nlev, nphi] (absent when only_flux), u0 [P, K, NQuad, nlev], flux_up, flux_down_diffuse,
     flux_down_direct [P, K, nlev], tau_arr [P, G, L]); the K axis is dropped when ``weights`` was [G].  actinic=True adds
     flux_act_up, flux_act_down_diffuse, flux_act_down_direct [P, K, nlev] (``Plan.fetch_band_actinic``).  NT_cor as in
-    ``pydisort_band``: u is corrected per column on the device before it is reduced."""
+    ``pydisort_band``: u is corrected per column on the device before it is reduced.  mu [nmu] or [P, nmu]: adds the band
+    radiances at those polar-angle cosines, u_mu [P, K, nmu, nlev, nphi] (not with only_flux) and u0_mu [P, K, nmu, nlev]
+    (``BandSolution.u_at``, ``Plan.fetch_band_view``)."""
+    if mu is not None:
+        mu = view_angles(mu, np.shape(dtau_abs)[0] if np.ndim(dtau_abs) == 3 else 0, "P")
     if chunk_columns <= 0:  # (as solve_columns_streamed: windows of ~8 192 (column, mode) chains)
         modes = 1 if only_flux else int(NFourier or NLeg or NQuad)
         chunk_columns = max(64, 8192 // max(modes, 1))
@@ -282,6 +301,9 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
         out = plan.fetch_band(want=("u0", "flux") if only_flux else ("u", "u0", "flux"))
         if actinic:
             out.update(plan.fetch_band_actinic())
+        if mu is not None:
+            sol._set_view(mu)
+            out.update(plan.fetch_band_view(("u0",) if only_flux else ("u", "u0")))
     finally:
         plan.close()
     out = {k: sol._out(v) for k, v in out.items() if v is not None}

@@ -2,7 +2,7 @@
 reference solves one column per ``pydisort`` call)."""
 import numpy as np
 
-from ._engine import Plan
+from ._engine import Plan, view_angles
 from . import _nt
 from ._prepare import double_gauss, prepare_columns
 
@@ -148,6 +148,21 @@ class BatchSolution:
         deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         r = self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("act",), derivative=deriv)
         return r["flux_act_down_diffuse"], r["flux_act_down_direct"]
+
+    def u_at(self, mu, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """u at the polar-angle cosines mu [nmu] or [C, nmu] -> [C, nmu, ntau, nphi]: the reference's ``subroutines.interpolate(u)``
+        for the whole batch on the device -- barycentric polynomial interpolation in mu of the evaluated (Nakajima-Tanaka corrected)
+        u, each hemisphere on its own; mu > 0 looks up, every other mu, 0 included, down (``Plan.set_view``).  Only u_mu leaves the
+        device."""
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        self.plan.set_view(mu)
+        return self.plan.evaluate(self._tau(tau), phi, is_antiderivative_wrt_tau, want=("view_u",), derivative=deriv)["u_mu"]
+
+    def u0_at(self, mu, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """The azimuthal mean u0 at the polar-angle cosines mu [nmu] or [C, nmu] -> [C, nmu, ntau] (``u_at``)."""
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        self.plan.set_view(mu)
+        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("view_u0",), derivative=deriv)["u0_mu"]
 
 
 def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLeg=None, NFourier=None,
@@ -302,7 +317,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
 
 
 def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=False, out=None, numeric_errors="raise",
-                           *, tau_order=0, actinic=False):
+                           *, tau_order=0, actinic=False, mu=None):
     """Throughput form for large column counts: ONE plan holds the inputs and the results of all columns, the
     intermediates of the solve (~8 MB per cfg4 column) live for `chunk_columns` columns at a time (0: ~8 192 (column,
     mode) chains per window) and the device-to-host copies of a window overlap the kernels of the next (``Plan.run_fetch``).
@@ -322,11 +337,17 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
           batch too large to retain gets them host to host through the same window pipeline (``Plan.set_eval_order``).
     actinic : True adds flux_act_up, flux_act_down_diffuse, flux_act_down_direct [C, ntau] (``Plan.fetch_actinic``), formed on the
           device from the resident u0 in the same `tau_order`; u0 itself may then be left out of `out` (it is not copied).
+    mu : polar-angle cosines [nmu] or [C, nmu] (``Plan.set_view``): adds u_mu [C, nmu, ntau, nphi] (not with only_flux) and u0_mu
+          [C, nmu, ntau], interpolated on the device in the same `tau_order` (``Plan.fetch_view``).  u may then be left out of `out`:
+          it stays on the device and is neither copied nor returned.  A view array that is absent from `out` is allocated and ADDED
+          to the caller's dict; one that is present is checked like the others and filled in place.
     Returns dict(u [C, NQuad, ntau, nphi] (absent when only_flux), u0, flux_up, flux_down_diffuse, flux_down_direct)."""
     if tau_order not in (-1, 0, 1):
         raise ValueError("tau_order must be -1, 0 or +1.")
     tau = np.ascontiguousarray(np.asarray(tau, float))
     C, ntau = tau.shape
+    if mu is not None:
+        mu = view_angles(mu, C)
     if chunk_columns <= 0:
         # windows of ~8 192 (column, mode) chains: the two-stream window pipeline of the library does best there (256 cfg4
         # columns: +4 % over windows of 2 048, DESIGN.md section 7b); the library shrinks a window that does not fit the
@@ -348,18 +369,28 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
         if not only_flux:
             shapes["u"] = (C, Q, ntau, len(phi))
         act = {k: (C, ntau) for k in Plan._ACT} if actinic else {}
+        view = {}
+        if mu is not None:
+            plan.set_view(mu)
+            view["u0_mu"] = (C, mu.shape[-1], ntau)
+            if not only_flux:
+                view["u_mu"] = (C, mu.shape[-1], ntau, len(phi))
         if out is None:
             out = {k: np.empty(shp) for k, shp in shapes.items()}
         else:
-            for k, shp in list(shapes.items()) + list(act.items()):
+            for k, shp in list(shapes.items()) + list(act.items()) + list(view.items()):
                 a = out.get(k)
                 if a is None and actinic and (k == "u0" or k in act):
                     continue  # (with actinic=True the caller may leave u0 on the device; actinic arrays not given are allocated)
+                if a is None and view and (k == "u" or k in view):
+                    continue  # (with mu the caller may leave u on the device; view arrays not given are allocated)
                 if a is None or a.shape != shp or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"]:
                     raise ValueError(f"out[{k!r}] must be a C-contiguous float64 array of shape {shp}.")
         plan.run_fetch(out)
         if actinic:
             out.update(plan.fetch_actinic(out))
+        if view:
+            out.update({k: v for k, v in plan.fetch_view(("u0",) if only_flux else ("u", "u0"), out).items() if v is not None})
     finally:
         plan.close()
     return out
