@@ -245,6 +245,43 @@ int rtd_plan_set_columns_band(rtd_plan* plan, const rtd_band* band, const double
  * Call after rtd_plan_set_columns (whose bdrf_q / bdrf_q0 may then be NULL) and before rtd_plan_solve. */
 int rtd_plan_set_bdrf_samples(rtd_plan* plan, int32_t nphi, const double* rho_qq, const double* rho_q0);
 
+/* Parametric surface models: the samples themselves formed on the device, from the three or four numbers per pixel a land or ocean
+ * retrieval holds (csrc/rtd_surface.h has the formulas and their conditioning).  rho(mu, mu', dphi): mu the REFLECTED cosine, mu'
+ * the INCIDENT one, both in (0, 1]; dphi the difference of the PROPAGATION azimuths, as the reference's BDRF callables take it
+ * (pydisotest/6_test.py:11-24): backscatter -- the hot spot -- is at dphi = pi.  params is [rows][4], unused entries 0:
+ *   RTD_SURFACE_LAMBERT  albedo in [0, 1]                    no sampling: q^0 = albedo, q^m = 0 for m > 0 (nphi is only range-checked)
+ *   RTD_SURFACE_HAPKE    B0 >= 0, HH > 0, 0 < W <= 1         Hapke's soil as in DISORT's test problem 6
+ *   RTD_SURFACE_ROSSLI   f_iso, f_vol, f_geo >= 0            Ross-Thick / Li-Sparse-Reciprocal (h/b = 2, b/r = 1), CLAMPED at 0: the
+ *                                                            kernels are unbounded below at grazing angles (rho = -1.8 at the smallest
+ *                                                            node of 16 streams for the weights 0.3, 0.1, 0.05) and a negative
+ *                                                            reflectance is not a surface
+ *   RTD_SURFACE_RPV      rho0 >= 0, k > 0, |Theta| < 1, rho_c  Rahman-Pinty-Verstraete; Theta < 0 is backscattering
+ * every parameter finite.  All four are reciprocal and even in dphi: the cosine series of rtd_plan_set_bdrf_samples is complete.
+ * rows: 1 (one surface for all columns), C (one per column) or -- for rtd_plan_set_columns_band -- P (one per profile). */
+enum { RTD_SURFACE_LAMBERT = 0, RTD_SURFACE_HAPKE = 1, RTD_SURFACE_ROSSLI = 2, RTD_SURFACE_RPV = 3 };
+typedef struct { int32_t model, nphi, rows; const double* params; } rtd_surface;
+
+/* Sticky, in the manner of rtd_plan_request_nt; the parameters are copied.  NULL or model < 0 withdraws the request.  RTD_ERR_ARG
+ * for a plan with nbdrf = 0, for inadmissible parameters (the message names the first bad row), or unless
+ * 2 (NBDRF - 1) < nphi <= 16384.  While a request is set, rtd_plan_set_columns_raw, _thermal and _band form bdrf_q and bdrf_q0 on the
+ * device where they otherwise upload them -- AHEAD of the thermal kernels, so Kirchhoff's law with emissivity = NULL reads the
+ * device-formed zeroth mode -- by rtd_surface_samples_kernel, one thread per sample at dphi_p = 2 pi p / nphi with mu' the nodes and
+ * the column's raw mu0, and rtd_bdrf_modes_kernel, in chunks of columns whose samples fit a scratch block from the pool (RTD_SURFACE_BYTES,
+ * default 256 MiB; one column at least); the tables do not depend on the chunk size.  Those calls then take bdrf_q = bdrf_q0 = NULL
+ * (a table: RTD_ERR_ARG), return RTD_ERR_STATE before rtd_plan_set_quadrature, RTD_ERR_ARG when rows fits neither 1, C nor (a band) P
+ * or when a plan with a beam meets a mu0 outside (0, 1]; a plan without a beam skips the mu0 column (bdrf_q0 stays 0).  The
+ * host-prepared rtd_plan_set_columns / _local return RTD_ERR_STATE while a request is set.  A later rtd_plan_set_bdrf_samples still
+ * overwrites the tables.  A plan that never requests allocates and launches nothing for this. */
+int rtd_plan_request_surface(rtd_plan* plan, const rtd_surface* surface);
+/* The plan-free form, like rtd_planck_band: rho[r][p] = rho(mu[r], mup[r], 2 pi p / nphi) with params[r][4], r < n, by the kernel
+ * the plans use (the same bits); host arrays in, host array out, synchronous.  RTD_ERR_ARG for an unknown model, inadmissible
+ * parameters, a cosine outside (0, 1] or nphi outside 1 ... 16384. */
+int rtd_surface_samples(int32_t device, int32_t model, int64_t n, const double* params, const double* mu, const double* mup,
+                        int32_t nphi, double* rho);
+/* Diagnostic, in the spirit of rtd_plan_get_nt: the BDRF tables as the plan holds them, uploaded or device-formed, unpadded:
+ * q [C][NBDRF][N][N], q0 [C][NBDRF][N]; either pointer may be NULL.  RTD_ERR_STATE before the columns.  Synchronous. */
+int rtd_plan_get_bdrf(rtd_plan* plan, double* q, double* q0);
+
 /* Fourier-mode shard (the partition for fewer columns than GPUs): the plan's nfourier local modes
  * stand for the modes first, first + stride, ... of `total` (the reference's NFourier; modes are independent through
  * the eigen stage and the boundary-condition solve, _gen_part.py:91, _coeffs.py:111, and meet only in the Fourier sum,
@@ -530,6 +567,8 @@ enum {
  *   RTD_WORK_BYTES        bytes of solve intermediates per plan (default 24 GiB): sizes the automatic column window
  *   RTD_POOL_BYTES        bytes of device memory (per device) of destroyed plans kept for the next plan in blocks above 64 MB
  *                         (default 0: large blocks go straight back to the runtime); the same as rtd_pool_set_limit
+ *   RTD_SURFACE_BYTES     bytes of the scratch block in which the surface models' samples are formed, chunk of columns after chunk
+ *                         (default 256 MiB; one column at least): rtd_plan_request_surface, rtd_surface_samples
  *   RTD_NO_PIPELINE       windows one after the other on one stream (no second hand-off slot, no eigen stream)
  *   RTD_BC_FORCE_PIVOT    fused boundary-condition kernels: =1 every elimination is redone by the column-pivoted LDS path (the
  *                         path of a failed speculation); =2 every chain of the 32-stream kernel takes the register-resident

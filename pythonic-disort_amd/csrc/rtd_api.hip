@@ -19,6 +19,7 @@
 #include "rtd_dd.h"
 #include "rtd_planck.h"
 #include "rtd_nt_prep.h"
+#include "rtd_surface.h"
 
 namespace {
 
@@ -344,6 +345,12 @@ struct rtd_plan {
   bool have_nt = false, nt_tables_ready = false;
   int nt_request = 0;   // rtd_plan_request_nt: nleg_all of the device-formed inputs (0: none); sticky
   int64_t nt_rows = 0;  // rows of nt_w: C, or the P profiles of a band
+  // Parametric surface (rtd_plan_request_surface): while surf_model >= 0 the raw uploads form bdrf_q / bdrf_q0 on the device from
+  // surf_par [surf_rows][4] (the caller's parameters, copied) instead of taking tables; sticky.  Nothing is held on the device
+  // between uploads: the scratch block of the samples and the staged parameters go back to the pool with the upload's staging block.
+  int surf_model = -1, surf_nphi = 0;
+  int64_t surf_rows = 0;
+  std::vector<double> surf_par;
   // RCCL communicator (one rank per GPU)
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_size = 0;
@@ -375,10 +382,13 @@ struct rtd_plan {
   //   member           entry points                                    FORK TABLES QUAD_T NT_T SOLUTION IFACE
   //   new_quadrature   rtd_plan_set_quadrature                         yes  yes    yes    yes  yes      -      and have_quad
   //   new_columns      set_columns_impl, set_columns_raw_impl          yes  yes    -      yes  yes      yes    and have_cols, band_cols
+  //   (none)           rtd_plan_request_surface                        -    -      -      -    -        -      host state only
   //   solution_stale   rtd_plan_set_bdrf_samples, _solve_layers        -    -      -      -    yes      -
   //   new_mode_shard   rtd_plan_set_mode_shard                         -    yes    yes    -    yes      -
   //   fresh_tables     rtd_plan_invalidate_tables                      yes  yes    yes    -    -        -
   //   touches_handoff  _set_bdrf_samples, _solve_layers, _get_tensors  yes  -      -      -    -        -      EARLY
+  // rtd_plan_request_surface changes what the NEXT raw upload does and nothing the plan holds: the tables it makes the upload form
+  // are covered by that upload's new_columns, as uploaded tables are.
   // DELIBERATE: the surface samples leave the tables valid (they do not read the surface), and solve_layers has just made them; the
   // mode shard neither forks (it queues nothing on `stream`) nor touches the NT tables (they hold no mode); invalidate_tables keeps the
   // solution fetchable.  EARLY: raised before the arguments are validated, so a REFUSED call (plan not solved, nbdrf = 0, several
@@ -784,7 +794,7 @@ extern "C" {
 
 int rtd_comm_destroy(rtd_plan* p);
 
-int rtd_version(void) { return 216; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt; 216: rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view, bit 3 of the evaluation flag word
+int rtd_version(void) { return 217; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt; 216: rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view, bit 3 of the evaluation flag word; 217: rtd_plan_request_surface, rtd_surface_samples, rtd_plan_get_bdrf
 
 const char* rtd_last_error(void) { return g_err.c_str(); }
 
@@ -1119,8 +1129,13 @@ extern "C++" std::vector<double> pad_streams(const double* src, int64_t blocks, 
 }
 
 // The argument checks shared by the prepared and the raw uploads (two parts: each upload has checks of its own between them)
-int refuse_missing_sources(const RtdDev& d, bool spoly_needed, const double* s_poly, const double* bdrf_q, const double* bdrf_q0) {
+int refuse_missing_sources(const RtdDev& d, bool spoly_needed, const double* s_poly, const double* bdrf_q, const double* bdrf_q0,
+                           bool surface_requested = false) {
   if (spoly_needed && !s_poly) return fail(RTD_ERR_ARG, "s_poly is required when nscoeffs > 0");
+  if (surface_requested) {  // (rtd_plan_request_surface: the tables are formed on the device)
+    if (bdrf_q || bdrf_q0) return fail(RTD_ERR_ARG, "rtd_plan_request_surface is set: bdrf_q and bdrf_q0 must be NULL");
+    return 0;
+  }
   if (d.NBDRF > 0 && (!bdrf_q || !bdrf_q0)) return fail(RTD_ERR_ARG, "BDRF tables are required when nbdrf > 0");
   return 0;
 }
@@ -1157,6 +1172,8 @@ int set_columns_impl(rtd_plan* p, const double* scaled_omega, const double* tau,
   if (!p || !scaled_omega || !tau || !taus0 || !scale_tau || !wleg || !mu0 || !I0 || !phi0 || !rescale)
     return fail(RTD_ERR_ARG, "null argument");
   const RtdDev& d = p->d;
+  if (p->surf_model >= 0)
+    return fail(RTD_ERR_STATE, "rtd_plan_request_surface is set: the BDRF modes are formed by the raw uploads (set_columns_raw / _thermal / _band)");
   if (int rc = refuse_missing_sources(d, d.Ns > 0, s_poly, bdrf_q, bdrf_q0)) return rc;
   if (p->nt_request > 0)
     return fail(RTD_ERR_STATE, "rtd_plan_request_nt is set: the Nakajima-Tanaka inputs are formed from raw columns (set_columns_raw / _thermal / _band)");
@@ -1293,6 +1310,64 @@ struct RtdThermalDev {
 __global__ void rtd_planck_band_kernel(long n, const double* T, const double* lo, const double* hi, double* out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = rtd_planck_band(T[i], lo[i], hi[i]);
+}
+
+// Parametric surface models (include/rtd.h: rtd_surface; the math is csrc/rtd_surface.h).  One thread per sample rho(mu, mu',
+// 2 pi p / nphi), the azimuth index p fastest; no LDS, no barrier, no cross-lane operation (the stand-in runtime of tests/cpu runs
+// the kernel thread by thread).  ONE kernel for both callers, so the bits of a sample cannot differ between them:
+//   N > 0   the rows of a plan's chunk of `cnt` columns from c0 on, laid out as rtd_bdrf_modes_kernel reads them: cnt N N rows
+//           (c, i, j) -> rho(mu_i, mu_j), then -- mu0 not null -- cnt N rows (c, i) -> rho(mu_i, mu0[c0 + c]) with the STAGED raw mu0;
+//           the parameter row of column c0 + c is (c0 + c) / group, or 0 when the surface is shared (par_rows = 1);
+//   N = 0   the plan-free rows: mu[r], mup[r] and par[r][4] as given.
+struct RtdSurfDev {
+  int model, nphi, N, group;
+  long nrows, cnt, c0, par_rows;
+  const double* par;        // [par_rows][4]
+  const double *mu, *mup;   // N > 0: the plan's nodes (d.mu) and the raw mu0 [C] (null: no mu0 rows); N = 0: [nrows] each
+  double* out;              // [nrows][nphi]
+};
+
+__global__ void rtd_surface_samples_kernel(RtdSurfDev v) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= v.nrows * v.nphi) return;
+  long r = idx / v.nphi;
+  const int p = (int)(idx % v.nphi);
+  double mu, mup;
+  long prow;
+  if (v.N > 0) {
+    const long N = v.N, nqq = v.cnt * N * N;
+    long c;
+    if (r < nqq) {
+      c = r / (N * N);
+      mu = v.mu[(r / N) % N];
+      mup = v.mu[r % N];
+    } else {
+      r -= nqq;
+      c = r / N;
+      mu = v.mu[r % N];
+      mup = v.mup[v.c0 + c];
+    }
+    prow = v.par_rows == 1 ? 0 : (v.c0 + c) / v.group;
+  } else {
+    mu = v.mu[r];
+    mup = v.mup[r];
+    prow = r;
+  }
+  double c, s;
+  rtd_surface_cs(2.0 * (double)p / (double)v.nphi, &c, &s);
+  v.out[idx] = rtd_surface_rho(v.model, v.par + 4 * prow, mu, mup, c, s);
+}
+
+// A Lambertian surface needs no sampling: q^0 = albedo at the N real nodes of every column of the (zeroed) tables, q^m = 0 beyond.
+// One thread per (c, i, j), j fastest; j = N stands for the mu0 column (skipped when with_q0 = 0).
+__global__ void rtd_surface_lambert_kernel(RtdDev d, RtdSurfDev v, int with_q0) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long N = d.N, NP = d.NP, NB = d.NBDRF;
+  if (idx >= (long)d.C * N * (N + 1)) return;
+  const long c = idx / (N * (N + 1)), i = (idx / (N + 1)) % N, j = idx % (N + 1);
+  const double albedo = v.par[4 * (v.par_rows == 1 ? 0 : c / v.group)];
+  if (j < N) const_cast<double*>(d.bdrfq)[(c * NB * NP + i) * NP + j] = albedo;
+  else if (with_q0) const_cast<double*>(d.bdrfq0)[c * NB * NP + i] = albedo;
 }
 
 __global__ void rtd_thermal_emission_kernel(RtdDev d, RtdThermalDev t) {
@@ -1643,7 +1718,154 @@ __global__ void rtd_view_apply_kernel(const double* l, long lstride, const int* 
   out[idx] = acc;
 }
 
+// The scratch budget of the surface samples in doubles (RTD_SURFACE_BYTES, default 256 MiB), and how a plan's upload spends it: the
+// staged parameters first, then the samples of `chunk` columns at a time -- as many as fit, at least one.
+int64_t surface_budget() {
+  const char* env = getenv("RTD_SURFACE_BYTES");
+  return std::max<long long>(env ? atoll(env) : (256ll << 20), 8) / 8;
+}
+struct SurfLayout {
+  int64_t par = 0, per_col = 0, chunk = 0;
+  int64_t total() const { return par + chunk * per_col; }
+};
+void surface_layout(const rtd_plan* p, SurfLayout* out) {
+  const RtdDev& d = p->d;
+  SurfLayout l;
+  l.par = (int64_t)p->surf_par.size();
+  if (p->surf_model != RTD_SURFACE_LAMBERT) {
+    l.per_col = ((int64_t)d.N * d.N + (d.beam ? d.N : 0)) * p->surf_nphi;
+    l.chunk = std::min<int64_t>(d.C, std::max<int64_t>(1, surface_budget() / l.per_col));
+  }
+  *out = l;
+}
+
+// bdrf_q / bdrf_q0 of all columns from the requested surface, queued on s behind the quadrature and the staged raw mu0 [C]: the
+// tables are zeroed as rtd_plan_set_bdrf_samples zeroes them, then chunk after chunk is sampled into the scratch block and reduced
+// by rtd_bdrf_modes_kernel under a descriptor shifted to the chunk's columns, as the windows shift theirs.  One wavefront reduces one
+// sample vector whatever the chunk: the result does not depend on the chunk size.  group: columns per parameter row.
+hipError_t surface_tables(const rtd_plan* p, const double* mu0_raw, int group, double* blk, const SurfLayout& lay, hipStream_t s) {
+  const RtdDev& d = p->d;
+  const int64_t C = d.C, N = d.N, NP = d.NP, NB = d.NBDRF;
+  hipError_t e = hipMemcpyAsync(blk, p->surf_par.data(), (size_t)lay.par * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(const_cast<double*>(d.bdrfq), 0, (size_t)(C * NB * NP * NP) * 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(const_cast<double*>(d.bdrfq0), 0, (size_t)(C * NB * NP) * 8, s);
+  if (e != hipSuccess) return e;
+  RtdSurfDev v{};
+  v.model = p->surf_model; v.nphi = p->surf_nphi; v.N = (int)N; v.group = group; v.par_rows = p->surf_rows;
+  v.par = blk; v.mu = d.mu; v.mup = d.beam ? mu0_raw : nullptr;
+  if (v.model == RTD_SURFACE_LAMBERT) {
+    const int64_t n = C * N * (N + 1);
+    hipLaunchKernelGGL(rtd_surface_lambert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, v, d.beam ? 1 : 0);
+    return hipGetLastError();
+  }
+  v.out = blk + lay.par;
+  for (int64_t c0 = 0; c0 < C && e == hipSuccess; c0 += lay.chunk) {
+    const int64_t cnt = std::min<int64_t>(lay.chunk, C - c0), nqq = cnt * N * N * v.nphi;
+    v.c0 = c0; v.cnt = cnt; v.nrows = cnt * (N * N + (d.beam ? N : 0));
+    hipLaunchKernelGGL(rtd_surface_samples_kernel, dim3((unsigned)((v.nrows * v.nphi + 255) / 256)), dim3(256), 0, s, v);
+    RtdDev w = d;
+    w.C = (int)cnt; w.bdrfq += c0 * NB * NP * NP; w.bdrfq0 += c0 * NB * NP;
+    rtd_launch_bdrf_modes(w, v.nphi, v.out, d.beam ? v.out + nqq : nullptr, s);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+// first row of params [rows][4] that `model` does not admit, with what is wrong in *why; -1: none
+int64_t surface_bad_row(int model, int64_t rows, const double* params, const char** why) {
+  for (int64_t r = 0; r < rows; ++r)
+    if ((*why = rtd_surface_bad(model, params + 4 * r))) return r;
+  return -1;
+}
+
 }  // namespace
+
+int rtd_plan_request_surface(rtd_plan* p, const rtd_surface* sf) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (!sf || sf->model < 0) {  // withdrawn: the next upload takes tables again
+    p->surf_model = -1;
+    p->surf_par.clear();
+    p->surf_rows = 0;
+    return 0;
+  }
+  const RtdDev& d = p->d;
+  if (d.NBDRF <= 0) return fail(RTD_ERR_ARG, "request_surface: the plan was created with nbdrf = 0");
+  if (sf->model >= RTD_SURFACE_NMODELS || sf->rows < 1 || !sf->params) return fail(RTD_ERR_ARG, "request_surface: unknown model, rows < 1 or null params");
+  if (!(2 * ((int64_t)d.NBDRF - 1) < sf->nphi && sf->nphi <= 16384)) return fail(RTD_ERR_ARG, "request_surface: need 2 (nbdrf - 1) < nphi <= 16384");
+  const char* why = nullptr;
+  const int64_t bad = surface_bad_row(sf->model, sf->rows, sf->params, &why);
+  if (bad >= 0) return fail(RTD_ERR_ARG, std::string("request_surface: row ") + std::to_string(bad) + ": " + why);
+  p->surf_model = sf->model;
+  p->surf_nphi = sf->nphi;
+  p->surf_rows = sf->rows;
+  p->surf_par.assign(sf->params, sf->params + (size_t)sf->rows * 4);
+  return 0;
+}
+
+int rtd_surface_samples(int32_t device, int32_t model, int64_t n, const double* params, const double* mu, const double* mup, int32_t nphi,
+                        double* rho) {
+  if (n < 0 || nphi < 1 || nphi > 16384 || (n > 0 && (!params || !mu || !mup || !rho)))
+    return fail(RTD_ERR_ARG, "surface_samples: null argument, n < 0 or nphi outside 1 ... 16384");
+  if (model < 0 || model >= RTD_SURFACE_NMODELS) return fail(RTD_ERR_ARG, "surface_samples: unknown model");
+  const char* why = nullptr;
+  const int64_t bad = surface_bad_row(model, n, params, &why);
+  if (bad >= 0) return fail(RTD_ERR_ARG, std::string("surface_samples: row ") + std::to_string(bad) + ": " + why);
+  for (int64_t r = 0; r < n; ++r)
+    if (!(mu[r] > 0.0 && mu[r] <= 1.0 && mup[r] > 0.0 && mup[r] <= 1.0))
+      return fail(RTD_ERR_ARG, "surface_samples: row " + std::to_string(r) + ": mu and mup must lie in (0, 1]");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(device));
+  const int64_t chunk = std::min<int64_t>(n, std::max<int64_t>(1, surface_budget() / (nphi + 6)));  // rows per pass
+  void* buf_v = nullptr;
+  size_t got = 0;
+  HIP_TRY(pooled_malloc(&buf_v, (size_t)(chunk * (nphi + 6)) * 8, device, &got));
+  double* buf = (double*)buf_v;
+  hipError_t e = hipSuccess;
+  for (int64_t r0 = 0; r0 < n && e == hipSuccess; r0 += chunk) {
+    const int64_t cnt = std::min<int64_t>(chunk, n - r0);
+    RtdSurfDev v{};
+    v.model = model; v.nphi = nphi; v.N = 0; v.group = 1; v.nrows = cnt; v.cnt = cnt; v.par_rows = cnt;
+    v.par = buf; v.mu = buf + 4 * cnt; v.mup = buf + 5 * cnt; v.out = buf + 6 * cnt;
+    e = hipMemcpy(buf, params + 4 * r0, (size_t)cnt * 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 4 * cnt, mu + r0, (size_t)cnt * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 5 * cnt, mup + r0, (size_t)cnt * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(rtd_surface_samples_kernel, dim3((unsigned)((cnt * nphi + 255) / 256)), dim3(256), 0, (hipStream_t)0, v);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(rho + r0 * nphi, v.out, (size_t)(cnt * nphi) * 8, hipMemcpyDeviceToHost);  // (waits for the kernel)
+    else (void)hipStreamSynchronize((hipStream_t)0);
+  }
+  pooled_free(buf, got, device);
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("surface_samples: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int rtd_plan_get_bdrf(rtd_plan* p, double* q, double* q0) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (!p->have_cols) return fail(RTD_ERR_STATE, "get_bdrf: no columns are set");
+  const RtdDev& d = p->d;
+  const int64_t C = d.C, N = d.N, NP = d.NP, NB = d.NBDRF;
+  if (NB <= 0 || (!q && !q0)) return 0;
+  HIP_TRY(hipSetDevice(p->device));
+  std::vector<double> h((size_t)(C * NB * NP * (q ? NP : 1)));
+  hipStream_t s = p->stream;
+  if (q) {  // rows and columns padded from N to NP on the device
+    HIP_TRY(hipMemcpyAsync(h.data(), d.bdrfq, (size_t)(C * NB * NP * NP) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t b = 0; b < C * NB; ++b)
+      for (int64_t i = 0; i < N; ++i)
+        for (int64_t j = 0; j < N; ++j) q[(b * N + i) * N + j] = h[(size_t)((b * NP + i) * NP + j)];
+  }
+  if (q0) {
+    HIP_TRY(hipMemcpyAsync(h.data(), d.bdrfq0, (size_t)(C * NB * NP) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t b = 0; b < C * NB; ++b)
+      for (int64_t i = 0; i < N; ++i) q0[b * N + i] = h[(size_t)(b * NP + i)];
+  }
+  p->stream_drained();
+  return 0;
+}
 
 int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wvnmlo, const double* wvnmhi, double* out) {
   if (n < 0 || (n > 0 && (!T || !wvnmlo || !wvnmhi || !out))) return fail(RTD_ERR_ARG, "planck_band: null argument or n < 0");
@@ -1702,7 +1924,16 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     if (th->btemp && !th->emissivity && d.NBDRF > 0 && !p->have_quad)
       return fail(RTD_ERR_STATE, "thermal: set_quadrature must precede the Kirchhoff emissivity");
   }
-  if (int rc = refuse_missing_sources(d, !th && d.Ns > 0, s_poly, bdrf_q, bdrf_q0)) return rc;
+  const bool surf = p->surf_model >= 0;  // the BDRF tables are formed here, from the requested surface (rtd_plan_request_surface)
+  if (int rc = refuse_missing_sources(d, !th && d.Ns > 0, s_poly, bdrf_q, bdrf_q0, surf)) return rc;
+  if (surf) {
+    if (!p->have_quad) return fail(RTD_ERR_STATE, "request_surface: set_quadrature must precede the columns");
+    if (!(p->surf_rows == 1 || p->surf_rows == d.C || (band && p->surf_rows == band->nprofiles)))
+      return fail(RTD_ERR_ARG, "request_surface: rows must be 1, ncols or (a band) nprofiles");
+    if (d.beam)
+      for (int64_t c = 0; c < d.C; ++c)
+        if (!(mu0[c] > 0.0 && mu0[c] <= 1.0)) return fail(RTD_ERR_ARG, "request_surface: mu0 must lie in (0, 1] when the plan has a beam");
+  }
   HIP_TRY(hipSetDevice(p->device));
   const int64_t C = d.C, L = d.L, M = d.M, N = d.N, NP = d.NP, Ns = d.Ns, NB = d.NBDRF;
   if (int rc = refuse_beam(d, I0)) return rc;
@@ -1727,6 +1958,19 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   size_t raw_got = 0;
   HIP_TRY(pooled_malloc(&raw_v, (size_t)total * 8, p->device, &raw_got));
   double* raw = (double*)raw_v;
+  // the surface's scratch block (parameters, then the samples of one chunk of columns) likewise; both go back together
+  SurfLayout sl;
+  if (surf) surface_layout(p, &sl);
+  void* surf_v = nullptr;
+  size_t surf_got = 0;
+  if (surf) {
+    const hipError_t es = pooled_malloc(&surf_v, (size_t)sl.total() * 8, p->device, &surf_got);
+    if (es != hipSuccess) {
+      (void)hipGetLastError();
+      pooled_free(raw, raw_got, p->device);
+      return fail(RTD_ERR_HIP, std::string("request_surface: scratch block of ") + std::to_string(sl.total() * 8) + " bytes: " + hipGetErrorString(es));
+    }
+  }
   RtdRaw r{};
   r.nleg_all = nleg_all;
   double* q = raw;
@@ -1780,7 +2024,9 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     }
   }
   std::vector<double> qh, q0h;
-  if (e == hipSuccess && NB > 0) {  // BDRF tables: padded from N to NP on the host (small)
+  if (e == hipSuccess && surf) {  // BDRF tables from the surface model; the rows of a band's P profiles serve its G points each
+    e = surface_tables(p, r.mu0, band && p->surf_rows != C ? (int)bG : 1, (double*)surf_v, sl, s);
+  } else if (e == hipSuccess && NB > 0) {  // BDRF tables: padded from N to NP on the host (small)
     qh = pad_streams(bdrf_q, C * NB, true, N, NP);
     q0h = pad_streams(bdrf_q0, C * NB, false, N, NP);
     e = hipMemcpyAsync((void*)d.bdrfq, qh.data(), qh.size() * 8, hipMemcpyHostToDevice, s);
@@ -1815,6 +2061,7 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   else (void)hipStreamSynchronize(s);  // nothing may still read the block when it goes back to the pool
   pooled_free(raw, raw_got, p->device);
+  if (surf) pooled_free(surf_v, surf_got, p->device);
   if (e != hipSuccess) {
     if (band) p->h_tau.clear();
     return fail(RTD_ERR_HIP, std::string("set_columns_raw: ") + hipGetErrorString(e));

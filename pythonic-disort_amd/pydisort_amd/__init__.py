@@ -9,6 +9,7 @@ from .batch import pydisort_batch, BatchSolution, solve_columns_streamed  # noqa
 from . import subroutines  # noqa: F401
 from .band import pydisort_band, BandSolution, solve_band_streamed  # noqa: F401
 from ._engine import Plan as _Plan, planck_band, band_mix  # noqa: F401
+from ._surface import surface_reflectance  # noqa: F401
 
 import contextlib as _contextlib
 
@@ -31,4 +32,4 @@ def pooled(nbytes=-1, device=0):
 
 
 __all__ = ["pydisort", "pydisort_batch", "BatchSolution", "solve_columns_streamed", "pydisort_band", "BandSolution",
-           "solve_band_streamed", "band_mix", "subroutines", "planck_band", "pool_bytes", "pool_trim", "pool_set_limit", "pooled"]
+           "solve_band_streamed", "band_mix", "subroutines", "planck_band", "surface_reflectance", "pool_bytes", "pool_trim", "pool_set_limit", "pooled"]

@@ -44,6 +44,8 @@ class Plan:
         _lib.check(lib.rtd_plan_set_quadrature(h, _lib.dptr(mu), _lib.dptr(w)))
         if prep.get("nt"):
             self.request_nt(prep["nt"])
+        if prep.get("surface") is not None:
+            self.request_surface(prep["surface"]["model"], prep["surface"]["params"], prep["surface"]["nphi"])
         if prep.get("band") is not None:
             self.set_columns_band(prep["band"], prep["cols"], prep.get("thermal"))
         elif prep.get("raw") is not None and prep.get("thermal") is not None:
@@ -115,7 +117,9 @@ class Plan:
                 "b_pos": (Cn, M, N), "b_neg": (Cn, M, N), "s_poly": (Cn, L, Ns), "bdrf_q": (Cn, NB, N, N),
                 "bdrf_q0": (Cn, NB, N)}
         required = {"tau_arr", "omega_arr", "f_arr", "mu0", "I0", "phi0"} | ({"s_poly"} if Ns > 0 and _thermal is None else set()) \
-            | ({"bdrf_q", "bdrf_q0"} if NB > 0 else set())
+            | ({"bdrf_q", "bdrf_q0"} if NB > 0 and not self._surface_requested() else set())
+        if self._surface_requested() and (a["bdrf_q"] is not None or a["bdrf_q0"] is not None):
+            raise ValueError("raw batch does not match the plan: a surface is requested, bdrf_q and bdrf_q0 must be None")
         if a["leg"] is None or a["leg"].ndim != 3 or a["leg"].shape[:2] != (Cn, L) or a["leg"].shape[2] < p["P"]:
             raise ValueError(f"raw batch does not match the plan: leg must be [C = {Cn}, L = {L}, nleg_all >= {p['P']}]")
         for k, shape in want.items():
@@ -183,7 +187,9 @@ class Plan:
         a = {k: _f64(cols.get(k)) for k in ("mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")}
         want = {"mu0": (Cn,), "I0": (Cn,), "phi0": (Cn,), "b_pos": (Cn, M, N), "b_neg": (Cn, M, N), "bdrf_q": (Cn, NB, N, N),
                 "bdrf_q0": (Cn, NB, N)}
-        required = {"mu0", "I0", "phi0"} | ({"bdrf_q", "bdrf_q0"} if NB > 0 else set())
+        required = {"mu0", "I0", "phi0"} | ({"bdrf_q", "bdrf_q0"} if NB > 0 and not self._surface_requested() else set())
+        if self._surface_requested() and (a["bdrf_q"] is not None or a["bdrf_q0"] is not None):
+            raise ValueError("band batch does not match the plan: a surface is requested, bdrf_q and bdrf_q0 must be None")
         for k, shape in want.items():
             if a[k] is None:
                 if k in required:
@@ -445,6 +451,41 @@ class Plan:
         of moments of the raw batch, or of the band's species.  0 withdraws the request."""
         _lib.check(self._lib.rtd_plan_request_nt(self._h, int(nleg_all)))
         self._nt_request = max(int(nleg_all), 0)
+
+    def _surface_requested(self):
+        return getattr(self, "_surface", None) is not None
+
+    def request_surface(self, model, params=None, nphi=256):
+        """While a surface is requested, ``set_columns_raw`` / ``_thermal`` / ``_band`` form the plan's BDRF Fourier modes on the
+        device from a parametric model instead of taking ``bdrf_q`` / ``bdrf_q0`` (include/rtd.h: rtd_plan_request_surface; the
+        plan needs NBDRF > 0).  model: "lambert" | "hapke" | "rossli" | "rpv", or the id of include/rtd.h; params [npar] or
+        [rows, npar] (padded to 4 with zeros) with rows = 1, C or -- for a band -- P; nphi: azimuth samples per pair of cosines.
+        model=None withdraws the request.  The host-prepared ``set_columns`` is refused while a request is set."""
+        from . import _surface
+        if model is None:
+            _lib.check(self._lib.rtd_plan_request_surface(self._h, None))
+            self._surface = None
+            return
+        if isinstance(model, str):
+            if model.lower() not in _surface.MODELS:
+                raise ValueError(f"surface: unknown model {model!r} (known: {', '.join(_surface.MODELS)}).")
+            model = _surface.MODELS[model.lower()][0]
+        p = np.atleast_2d(np.asarray(params, dtype=np.float64))
+        if p.ndim != 2 or not 1 <= p.shape[1] <= 4:
+            raise ValueError("surface: params must be [npar] or [rows, npar] with npar <= 4.")
+        p4 = np.zeros((p.shape[0], 4))
+        p4[:, :p.shape[1]] = p
+        sf = _lib.rtd_surface(int(model), int(nphi), p4.shape[0], _lib.dptr(p4))
+        _lib.check(self._lib.rtd_plan_request_surface(self._h, C.byref(sf)))
+        self._surface = (int(model), int(nphi), p4.shape[0])
+
+    def get_bdrf(self):
+        """The BDRF tables as the plan holds them, uploaded or device-formed (include/rtd.h: rtd_plan_get_bdrf) ->
+        (q [C, NBDRF, N, N], q0 [C, NBDRF, N])."""
+        NB = self.prep["NBDRF"]
+        q, q0 = np.zeros((self.C, NB, self.N, self.N)), np.zeros((self.C, NB, self.N))
+        _lib.check(self._lib.rtd_plan_get_bdrf(self._h, _lib.dptr(q), _lib.dptr(q0)))
+        return q, q0
 
     def get_nt(self):
         """What the plan holds of the corrections' inputs, uploaded or device-formed (include/rtd.h: rtd_plan_get_nt) ->

@@ -37,6 +37,11 @@ class rtd_band(C.Structure):
                [(n, _dp) for n in ("dtau_abs", "dtau_spec", "omega_spec", "leg_spec")]
 
 
+class rtd_surface(C.Structure):
+    """A parametric surface for rtd_plan_request_surface (include/rtd.h: rtd_surface)."""
+    _fields_ = [("model", C.c_int32), ("nphi", C.c_int32), ("rows", C.c_int32), ("params", _dp)]
+
+
 # every symbol include/rtd.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "rtd_version": (C.c_int, []),
@@ -74,6 +79,9 @@ SIGNATURES = {
     "rtd_plan_fetch_view": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_fetch_band_view": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_set_bdrf_samples":(C.c_int, [_vp, C.c_int32, _dp, _dp]),
+    "rtd_plan_request_surface": (C.c_int, [_vp, C.POINTER(rtd_surface)]),
+    "rtd_surface_samples": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp, _dp, C.c_int32, _dp]),
+    "rtd_plan_get_bdrf": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_set_mode_shard": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "rtd_plan_invalidate_tables": (C.c_int, [_vp]),
     "rtd_plan_solve": (C.c_int, [_vp]),

@@ -11,6 +11,7 @@ import numpy as np
 from ._engine import Plan, view_angles
 from ._prepare import double_gauss
 from .batch import BatchSolution, _nt_checks, _retention, _thermal_inputs
+from ._surface import surface_request
 
 
 def level_tau(tau_arr, levels=None):
@@ -49,7 +50,7 @@ def _per_column(v, name, P, G, tail=()):
 
 
 def _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg, NFourier, delta_M, only_flux,
-                 b_pos, b_neg, bdrf_q, bdrf_q0, thermal):
+                 b_pos, b_neg, bdrf_q, bdrf_q0, thermal, surface=None, NBDRF=None):
     """Everything a user can get wrong is raised here, on the small arrays, before anything touches the device.
     -> (prep for ``Plan``, weights [K, G], whether the K axis is dropped)."""
     a, ds, om, leg = (np.asarray(v, float) for v in (dtau_abs, dtau_spec, omega_spec, Leg_spec))
@@ -136,6 +137,12 @@ def _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0
         NB = bq.shape[1]
         bq = np.ascontiguousarray(_per_column(bq, "bdrf_q", P, G, (NB, N, N)))
         bq0 = np.ascontiguousarray(_per_column(bdrf_q0, "bdrf_q0", P, G, (NB, N)))
+    sf = None
+    if surface is not None:
+        if bdrf_q is not None:
+            raise ValueError("Give either surface or bdrf_q / bdrf_q0, not both.")
+        sf = surface_request(surface, ((), (P,), (P, G)), f"one surface, one per profile or one per column: P = {P}, G = {G}", NFourier, NBDRF)
+        NB = sf["NBDRF"]
     th = None
     if thermal is not None:
         t = dict(thermal)
@@ -149,7 +156,7 @@ def _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0
     band = dict(dtau_abs=a, dtau_spec=ds, omega_spec=om, leg_spec=leg, delta_m=bool(delta_M))
     cols = dict(mu0=mu0c, I0=I0c, phi0=phi0c, b_pos=bp, b_neg=bn, bdrf_q=bq, bdrf_q0=bq0)
     prep = dict(C=C, L=L, N=N, P=NLeg, M=NFourier, Ns=2 if th is not None else 0, NBDRF=NB, beam=bool(np.any(I0c > 0)), mu=mu, W=W,
-                tau=None, raw=None, band=band, cols=cols, thermal=th)
+                tau=None, raw=None, band=band, cols=cols, thermal=th, surface=sf)
     return prep, w, squeeze
 
 
@@ -230,7 +237,8 @@ class BandSolution:
 
 def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=None, NFourier=None,
                   delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None, bdrf_q0=None, thermal=None, device=0,
-                  work_columns=0, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False, NT_cor=False):
+                  work_columns=0, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False, surface=None,
+                  NBDRF=None, NT_cor=False):
     """P profiles x G spectral points of a band in one call.
 
     dtau_abs [P, G, L]: absorption optical thickness of each layer at each spectral point; dtau_spec, omega_spec [P, L, S]:
@@ -243,6 +251,9 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
     weights: [G] or [K, G] -- k-distribution weights, several channels' response functions, photolysis cross sections.
     b_pos / b_neg (scalar, [.], [., N] or [., N, NFourier]), bdrf_q [., NBDRF, N, N], bdrf_q0 [., NBDRF, N] and the arrays of
     ``thermal`` (as in ``pydisort_batch``) are per profile, or per column where they differ by g.
+    surface=dict(model=..., params=[npar], [P, npar] or [P, G, npar], nphi=256) with NBDRF (default NFourier) instead of bdrf_q /
+    bdrf_q0: a parametric surface model whose modes the device forms, as in ``pydisort_batch``; parameters per profile are shared by
+    the profile's G columns on the device.
     NT_cor=True adds the Nakajima-Tanaka corrections to ``u`` before the spectral sum, their inputs formed on the device
     (``Plan.request_nt``): the mixture's full weighted phase function once per PROFILE ([P, L, NLeg_all] -- it does not depend on
     the spectral point), the IMS constants per column.  Needs delta_M, more moments in Leg_spec than NLeg, I0 > 0 in every column
@@ -250,7 +261,7 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
     Everything else as in ``pydisort_batch``.  Not combined with mode shards or communicators.
     Returns (mu_arr, BandSolution)."""
     prep, w, squeeze = _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg, NFourier, delta_M,
-                                    only_flux, b_pos, b_neg, bdrf_q, bdrf_q0, thermal)
+                                    only_flux, b_pos, b_neg, bdrf_q, bdrf_q0, thermal, surface, NBDRF)
     if numeric_errors not in ("raise", "nan"):
         raise ValueError('numeric_errors must be "raise" or "nan".')
     if NT_cor and not only_flux:
@@ -273,7 +284,8 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
 
 def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, levels=None, phi=None,
                         chunk_columns=0, NLeg=None, NFourier=None, delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None,
-                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False, mu=None, NT_cor=False):
+                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False, mu=None, surface=None,
+                        NBDRF=None, NT_cor=False):
     """Throughput form of ``pydisort_band`` (as ``solve_columns_streamed`` is of ``pydisort_batch``): ONE plan holds the inputs
     and the results of all P G columns, the intermediates of the solve live for `chunk_columns` columns at a time, the results at
     `levels` (None: all L + 1) and `phi` are reduced on the device and only the P band results travel to the host -- 1 / G of what
@@ -283,7 +295,7 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
     flux_act_up, flux_act_down_diffuse, flux_act_down_direct [P, K, nlev] (``Plan.fetch_band_actinic``).  NT_cor as in
     ``pydisort_band``: u is corrected per column on the device before it is reduced.  mu [nmu] or [P, nmu]: adds the band
     radiances at those polar-angle cosines, u_mu [P, K, nmu, nlev, nphi] (not with only_flux) and u0_mu [P, K, nmu, nlev]
-    (``BandSolution.u_at``, ``Plan.fetch_band_view``)."""
+    (``BandSolution.u_at``, ``Plan.fetch_band_view``).  surface, NBDRF as in ``pydisort_band``."""
     if mu is not None:
         mu = view_angles(mu, np.shape(dtau_abs)[0] if np.ndim(dtau_abs) == 3 else 0, "P")
     if chunk_columns <= 0:  # (as solve_columns_streamed: windows of ~8 192 (column, mode) chains)
@@ -292,7 +304,7 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
     _, sol = pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=NLeg, NFourier=NFourier,
                            delta_M=delta_M, only_flux=only_flux, b_pos=b_pos, b_neg=b_neg, bdrf_q=bdrf_q, bdrf_q0=bdrf_q0,
                            thermal=thermal, device=device, work_columns=chunk_columns, numeric_errors=numeric_errors, retain=False,
-                           _defer_solve=True, NT_cor=NT_cor)
+                           _defer_solve=True, NT_cor=NT_cor, surface=surface, NBDRF=NBDRF)
     plan = sol.plan
     try:
         phi = np.array([0.0]) if (only_flux or phi is None) else np.atleast_1d(np.asarray(phi, float))

@@ -5,6 +5,7 @@ import numpy as np
 from ._engine import Plan, view_angles
 from . import _nt
 from ._prepare import double_gauss, prepare_columns
+from ._surface import surface_request
 
 
 DEFAULT_RETAIN_BYTES = 16 << 30  # pydisort_batch(retain=..., retain_bytes=None): what a call may keep on the device for its evaluators
@@ -169,7 +170,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
                    b_pos=0, b_neg=0, only_flux=False, f_arr=0, NT_cor=False, bdrf_q=None, bdrf_q0=None,
                    s_poly_coeffs=None, device=0, bdrf_samples=None, NBDRF=None, mode_shard=None, work_columns=0,
                    device_prepare=False, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False,
-                   thermal=None):
+                   thermal=None, surface=None):
     """Like ``pydisort`` with a leading column axis on every atmospheric input:
     tau_arr, omega_arr, f_arr [C, L]; Leg_coeffs_all [C, L, NLeg_all]; mu0, I0, phi0 [C];
     b_pos / b_neg: scalar, [C], [C, N] or [C, N, NFourier]; s_poly_coeffs [C, L, Ns];
@@ -177,6 +178,13 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
     bdrf_samples=(rho_qq [C, N, N, nphi], rho_q0 [C, N, nphi] or None) instead: the reflectance itself sampled at
     dphi_p = 2 pi p / nphi; its first NBDRF (default NFourier) Fourier modes are then formed on the device
     (``subroutines.sample_BDRF`` builds the samples from a function rho(mu, mu', dphi)).
+    surface=dict(model="lambert" | "hapke" | "rossli" | "rpv", params=[npar] or [C, npar], nphi=256) instead: a parametric surface
+    model, stated in the few numbers a retrieval holds per pixel -- albedo; Hapke's B0, HH, W; the Ross-Li kernel weights f_iso, f_vol,
+    f_geo (clamped at 0: the kernels go negative at grazing angles); RPV's rho0, k, Theta, rho_c.  The device samples the reflectance
+    at the quadrature nodes and mu0 and forms its first NBDRF (default NFourier) modes (``Plan.request_surface``); no table or sample
+    array exists on the host.  rho(mu, mu', dphi) takes dphi as the reference's BDRF callables do: the hot spot is at dphi = pi.
+    Implies device_prepare=True; excludes bdrf_q, bdrf_samples and mode_shard.  With ``thermal`` and no emissivity, Kirchhoff's law
+    uses the device-formed zeroth mode.
     NT_cor=True adds the Nakajima-Tanaka corrections to ``u`` on the device (needs a beam in every column,
     f_arr > 0 and more Legendre coefficients than NLeg).
     mode_shard=(r, G): solve only the Fourier modes r, r + G, r + 2G, ... (the partition for
@@ -249,6 +257,14 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
             raise ValueError("The shape of a boundary condition is incorrect.")
         return out
 
+    sf = None
+    if surface is not None:
+        if bdrf_q is not None or bdrf_q0 is not None or bdrf_samples is not None:
+            raise ValueError("Give either surface or bdrf_q / bdrf_q0 / bdrf_samples, not both.")
+        if mode_shard is not None:
+            raise ValueError("surface cannot be combined with mode_shard.")
+        sf = surface_request(surface, ((), (C,)), f"one surface, or one per column: C = {C}", NFourier, NBDRF)
+        device_prepare = True
     th = None
     if thermal is not None:
         if s_poly_coeffs is not None:
@@ -281,8 +297,9 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
                    s_poly=sp if sp.shape[2] > 0 else None,
                    bdrf_q=bq if bq.shape[1] > 0 else None, bdrf_q0=bq0 if bq.shape[1] > 0 else None)
         mu, W = double_gauss(N)
-        prep = dict(C=C, L=L, N=N, P=NLeg, M=NFourier, Ns=2 if th is not None else sp.shape[2], NBDRF=bq.shape[1],
-                    beam=bool(np.any(I0 > 0)), mu=mu, W=W, tau=tau_arr, raw=raw, thermal=th, nt=nt_device)
+        prep = dict(C=C, L=L, N=N, P=NLeg, M=NFourier, Ns=2 if th is not None else sp.shape[2],
+                    NBDRF=bq.shape[1] if sf is None else sf["NBDRF"],
+                    beam=bool(np.any(I0 > 0)), mu=mu, W=W, tau=tau_arr, raw=raw, thermal=th, nt=nt_device, surface=sf)
     else:
         prep = prepare_columns(tau_arr, omega_arr, NQuad, Leg, mu0, I0, phi0, NLeg, NFourier, bc(b_pos), bc(b_neg),
                                f_arr, sp, bq, bq0)
@@ -325,6 +342,8 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
 
     cfg : dict of ``pydisort_batch`` keyword arguments with a leading column axis (tau_arr, omega_arr, Leg_coeffs_all,
           mu0, I0, phi0, optional f_arr, b_pos, b_neg, s_poly_coeffs, bdrf_q, bdrf_q0, NLeg, NFourier); NQuad scalar.
+          surface=dict(model=..., params=[npar] or [C, npar], nphi=256) in cfg (with NBDRF) forms the BDRF modes of all columns on
+          the device from a parametric model, as in ``pydisort_batch``.
           NT_cor=True in cfg adds the Nakajima-Tanaka corrections to u, their inputs formed on the device (ignored with only_flux).
     tau : [C, ntau] evaluation depths; phi : [nphi].
     out : optional dict of preallocated C-contiguous float64 result arrays to fill (the same keys and shapes).  Without `actinic`
