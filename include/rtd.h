@@ -256,14 +256,26 @@ int rtd_plan_set_bdrf_samples(rtd_plan* plan, int32_t nphi, const double* rho_qq
  *                                                            node of 16 streams for the weights 0.3, 0.1, 0.05) and a negative
  *                                                            reflectance is not a surface
  *   RTD_SURFACE_RPV      rho0 >= 0, k > 0, |Theta| < 1, rho_c  Rahman-Pinty-Verstraete; Theta < 0 is backscattering
- * every parameter finite.  All four are reciprocal and even in dphi: the cosine series of rtd_plan_set_bdrf_samples is complete.
- * rows: 1 (one surface for all columns), C (one per column) or -- for rtd_plan_set_columns_band -- P (one per profile). */
-enum { RTD_SURFACE_LAMBERT = 0, RTD_SURFACE_HAPKE = 1, RTD_SURFACE_ROSSLI = 2, RTD_SURFACE_RPV = 3 };
+ *   RTD_SURFACE_OCEAN    U >= 0, n > 1, rho_w >= 0           the wind-roughened ocean, Cox-Munk glint with isotropic slopes: wind speed U in
+ *                                                            m/s (sigma^2 = 0.003 + 0.00512 U), real refractive index n (unpolarized
+ *                                                            Fresnel), rho_w a Lambertian addition for underlight and foam.  The glint
+ *                                                            is at dphi = 0.  Shadowing (S = 1 / (1 + L(mu) + L(mu'))) is ALWAYS ON:
+ *                                                            without it the albedo at the smallest node exceeds 1 from 16 streams
+ *                                                            upward (4.8 at 34 streams, U = 5 m/s); with it the worst is 0.74
+ * every parameter finite.  All five are reciprocal and even in dphi: the cosine series of rtd_plan_set_bdrf_samples is complete.
+ * rows: 1 (one surface for all columns), C (one per column) or -- for rtd_plan_set_columns_band -- P (one per profile).
+ * The ocean does not take the uniform-grid route of the other models in a plan: the glint's azimuthal width at a grazing pair of 34
+ * or 64 streams is 1e-3 rad.  rtd_surface_ocean_kernel forms its modes in one pass per pair of cosines on the clustered periodic grid
+ * dphi = psi - a sin psi, psi_p = 2 pi p / nphi, weights (1 - a cos psi_p) / nphi, a per pair (csrc/rtd_surface.h defines it), straight
+ * into the tables: no samples in memory, no scratch block, no chunk, no RTD_SURFACE_BYTES.  For this model nphi is the number of
+ * psi nodes: even, >= 4 NBDRF (Nyquist on the coarsest spacing), <= 16384; 512 leaves <= 1.7e-9 of a pair's largest mode at 64
+ * streams (profiles/surface_ocean.json).  rtd_surface_samples keeps its uniform dphi grid for every model. */
+enum { RTD_SURFACE_LAMBERT = 0, RTD_SURFACE_HAPKE = 1, RTD_SURFACE_ROSSLI = 2, RTD_SURFACE_RPV = 3, RTD_SURFACE_OCEAN = 4 };
 typedef struct { int32_t model, nphi, rows; const double* params; } rtd_surface;
 
 /* Sticky, in the manner of rtd_plan_request_nt; the parameters are copied.  NULL or model < 0 withdraws the request.  RTD_ERR_ARG
  * for a plan with nbdrf = 0, for inadmissible parameters (the message names the first bad row), or unless
- * 2 (NBDRF - 1) < nphi <= 16384.  While a request is set, rtd_plan_set_columns_raw, _thermal and _band form bdrf_q and bdrf_q0 on the
+ * 2 (NBDRF - 1) < nphi <= 16384 (RTD_SURFACE_OCEAN: nphi even and 4 NBDRF <= nphi <= 16384).  While a request is set, rtd_plan_set_columns_raw, _thermal and _band form bdrf_q and bdrf_q0 on the
  * device where they otherwise upload them -- AHEAD of the thermal kernels, so Kirchhoff's law with emissivity = NULL reads the
  * device-formed zeroth mode -- by rtd_surface_samples_kernel, one thread per sample at dphi_p = 2 pi p / nphi with mu' the nodes and
  * the column's raw mu0, and rtd_bdrf_modes_kernel, in chunks of columns whose samples fit a scratch block from the pool (RTD_SURFACE_BYTES,

@@ -20,6 +20,12 @@
 #include "rtd_planck.h"
 #include "rtd_nt_prep.h"
 #include "rtd_surface.h"
+#if !defined(__HIPCC__)
+// A host compiler sees this unit only over the stand-in runtime of tests/cpu, which RUNS the kernels of the unit it compiles, thread
+// by thread on heap memory, and replaces the other units by shadow launchers.  The ocean's mode kernel joins this unit there (one
+// lane per pair of cosines, no cross-lane step), so its indexing and every table it writes are bounds-checked and checked by value.
+#include "rtd_surface_ocean.hip"
+#endif
 
 namespace {
 
@@ -1732,7 +1738,7 @@ void surface_layout(const rtd_plan* p, SurfLayout* out) {
   const RtdDev& d = p->d;
   SurfLayout l;
   l.par = (int64_t)p->surf_par.size();
-  if (p->surf_model != RTD_SURFACE_LAMBERT) {
+  if (p->surf_model != RTD_SURFACE_LAMBERT && p->surf_model != RTD_SURFACE_OCEAN) {  // (the ocean's kernel holds no samples in memory)
     l.per_col = ((int64_t)d.N * d.N + (d.beam ? d.N : 0)) * p->surf_nphi;
     l.chunk = std::min<int64_t>(d.C, std::max<int64_t>(1, surface_budget() / l.per_col));
   }
@@ -1756,6 +1762,10 @@ hipError_t surface_tables(const rtd_plan* p, const double* mu0_raw, int group, d
   if (v.model == RTD_SURFACE_LAMBERT) {
     const int64_t n = C * N * (N + 1);
     hipLaunchKernelGGL(rtd_surface_lambert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, v, d.beam ? 1 : 0);
+    return hipGetLastError();
+  }
+  if (v.model == RTD_SURFACE_OCEAN) {  // modes on the clustered grid, one pass per pair of cosines (csrc/rtd_surface_ocean.hip)
+    rtd_launch_surface_ocean(d, v.nphi, blk, p->surf_rows, group, mu0_raw, s);
     return hipGetLastError();
   }
   v.out = blk + lay.par;
@@ -1792,6 +1802,8 @@ int rtd_plan_request_surface(rtd_plan* p, const rtd_surface* sf) {
   if (d.NBDRF <= 0) return fail(RTD_ERR_ARG, "request_surface: the plan was created with nbdrf = 0");
   if (sf->model >= RTD_SURFACE_NMODELS || sf->rows < 1 || !sf->params) return fail(RTD_ERR_ARG, "request_surface: unknown model, rows < 1 or null params");
   if (!(2 * ((int64_t)d.NBDRF - 1) < sf->nphi && sf->nphi <= 16384)) return fail(RTD_ERR_ARG, "request_surface: need 2 (nbdrf - 1) < nphi <= 16384");
+  if (sf->model == RTD_SURFACE_OCEAN && (sf->nphi % 2 != 0 || sf->nphi < 4 * (int64_t)d.NBDRF))
+    return fail(RTD_ERR_ARG, "request_surface: the ocean's clustered grid needs an even nphi >= 4 nbdrf");
   const char* why = nullptr;
   const int64_t bad = surface_bad_row(sf->model, sf->rows, sf->params, &why);
   if (bad >= 0) return fail(RTD_ERR_ARG, std::string("request_surface: row ") + std::to_string(bad) + ": " + why);

@@ -130,5 +130,7 @@ void rtd_launch_eval(const RtdDev& d, const RtdEval& e, hipStream_t s);
 void rtd_launch_nt_tables(const RtdDev& d, const RtdNt& nt, hipStream_t s);
 void rtd_launch_nt_apply(const RtdDev& d, const RtdNt& nt, const RtdEval& e, hipStream_t s);
 void rtd_launch_bdrf_modes(const RtdDev& d, int nphi, const double* rho_qq, const double* rho_q0, hipStream_t s);
+void rtd_launch_surface_ocean(const RtdDev& d, int nphi, const double* par, long par_rows, int group, const double* mu0_raw,
+                              hipStream_t s);  // rtd_surface_ocean.hip: bdrfq / bdrfq0 of RTD_SURFACE_OCEAN on the clustered azimuth grid
 void rtd_launch_export(const RtdDev& d, int col, double* GC, double* K, double* B, double* Gim, double* G,
                        hipStream_t s);

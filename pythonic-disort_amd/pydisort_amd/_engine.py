@@ -458,7 +458,7 @@ class Plan:
     def request_surface(self, model, params=None, nphi=256):
         """While a surface is requested, ``set_columns_raw`` / ``_thermal`` / ``_band`` form the plan's BDRF Fourier modes on the
         device from a parametric model instead of taking ``bdrf_q`` / ``bdrf_q0`` (include/rtd.h: rtd_plan_request_surface; the
-        plan needs NBDRF > 0).  model: "lambert" | "hapke" | "rossli" | "rpv", or the id of include/rtd.h; params [npar] or
+        plan needs NBDRF > 0).  model: "lambert" | "hapke" | "rossli" | "rpv" | "ocean", or the id of include/rtd.h; params [npar] or
         [rows, npar] (padded to 4 with zeros) with rows = 1, C or -- for a band -- P; nphi: azimuth samples per pair of cosines.
         model=None withdraws the request.  The host-prepared ``set_columns`` is refused while a request is set."""
         from . import _surface

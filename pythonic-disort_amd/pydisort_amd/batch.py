@@ -178,7 +178,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
     bdrf_samples=(rho_qq [C, N, N, nphi], rho_q0 [C, N, nphi] or None) instead: the reflectance itself sampled at
     dphi_p = 2 pi p / nphi; its first NBDRF (default NFourier) Fourier modes are then formed on the device
     (``subroutines.sample_BDRF`` builds the samples from a function rho(mu, mu', dphi)).
-    surface=dict(model="lambert" | "hapke" | "rossli" | "rpv", params=[npar] or [C, npar], nphi=256) instead: a parametric surface
+    surface=dict(model="lambert" | "hapke" | "rossli" | "rpv" | "ocean", params=[npar] or [C, npar], nphi=256 (ocean: 512)) instead: a parametric surface
     model, stated in the few numbers a retrieval holds per pixel -- albedo; Hapke's B0, HH, W; the Ross-Li kernel weights f_iso, f_vol,
     f_geo (clamped at 0: the kernels go negative at grazing angles); RPV's rho0, k, Theta, rho_c.  The device samples the reflectance
     at the quadrature nodes and mu0 and forms its first NBDRF (default NFourier) modes (``Plan.request_surface``); no table or sample
