@@ -22,6 +22,61 @@ def view_angles(mu, rows, axis="C"):
     return mu
 
 
+_RESULT = ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")  # the C ABI's order of the result pointers
+_THERMAL = ("TEMPER", "WVNMLO", "WVNMHI", "BTEMP", "TTEMP", "TEMIS", "emissivity")  # the fields of rtd_thermal, in their order
+
+
+def _result_arrays(lead, Q, ntau, nphi, want=None):
+    """The result dictionary of the fetches and evaluations: u `lead` + [Q, ntau, nphi], u0 `lead` + [Q, ntau], the three fluxes
+    `lead` + [ntau].  want: what is allocated of ("u", "u0", "flux"), the rest is None, and so is u without azimuths; None: all of
+    it, as the fetches of the stored points return it.  (``Plan.evaluate`` alone spells its arrays out: it is timed per call.)"""
+    every = want is None
+    field, level = lead + (Q, ntau), lead + (ntau,)
+    fl = [np.empty(level) if every or "flux" in want else None for _ in range(3)]
+    return {"u": np.empty(field + (nphi,)) if every or ("u" in want and nphi > 0) else None,
+            "u0": np.empty(field) if every or "u0" in want else None, "flux_up": fl[0], "flux_down_diffuse": fl[1], "flux_down_direct": fl[2]}
+
+
+def _out_int(fn, *args, ctype=C.c_int64):
+    """The integer that a C entry point returns through its last argument."""
+    b = ctype()
+    _lib.check(fn(*args, C.byref(b)))
+    return b.value
+
+
+def _result_ptrs(out):
+    """The five result pointers of the C ABI, in its order, from a result dictionary (a missing or None entry: NULL)."""
+    return [_lib.dptr(out.get(k)) for k in _RESULT]
+
+
+def _out_arrays(given, shapes):
+    """name -> array of the shape `shapes` gives it: the caller's own of `given` (dict or None), checked and to be filled in place,
+    else freshly allocated."""
+    out = {}
+    for k, shape in shapes.items():
+        a = given.get(k) if given else None
+        if a is None:
+            a = np.empty(shape)
+        elif not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable and a.shape == shape):
+            raise ValueError(f"out[{k!r}] must be a writeable C-contiguous float64 array of the shape {shape}.")
+        out[k] = a
+    return out
+
+
+def _thermal_struct(thermal, Cn, L, N):
+    """The thermal dict of ``Plan.set_columns_thermal`` checked against the plan's (C, L, N) -> (rtd_thermal, the arrays it points
+    into: they must outlive the call that takes the struct)."""
+    shapes = dict(zip(_THERMAL, ((Cn, L + 1), (Cn,), (Cn,), (Cn,), (Cn,), (Cn,), (Cn, N))))
+    t = {k: _f64(thermal.get(k)) for k in _THERMAL}
+    for k, shape in shapes.items():
+        if t[k] is None:
+            if k in _THERMAL[:3]:
+                raise ValueError(f"thermal batch does not match the plan: {k} is required")
+        elif t[k].shape != shape:
+            raise ValueError(f"thermal batch does not match the plan: {k} has the shape {t[k].shape}, expected {shape}")
+    return _lib.rtd_thermal(*[_lib.dptr(t[k]) for k in _THERMAL]), t
+
+
 class Plan:
     def __init__(self, prep, device=0, work_columns=0, retain_bytes=0, retain_form=0):
         """prep: dict from _prepare.prepare_columns.  work_columns: columns whose intermediates are resident at a time
@@ -32,6 +87,18 @@ class Plan:
         2 lean (rtd_plan_create_retained_form)."""
         lib = _lib.load()
         self._lib = lib
+        # What later calls read, with its "nothing yet" value (the uploads below set some of it, so it comes first).
+        self.solved = False        # solve / run / run_fetch / solve_bc; every upload and shard call clears it
+        self._ev_shape = None      # (ntau, nphi) of the stored points: set_eval_points, evaluate_band
+        self._band = None          # (P, K): set_band_weights
+        self._view = None          # nmu: set_view
+        self._surface = None       # (model id, nphi, rows): request_surface
+        self._sharded = False      # set_mode_shard
+        self._nranks = None        # comm_init
+        self._nt_request = 0       # request_nt
+        self._nt_nleg_all = 0      # set_nt, or the set_columns_raw / _thermal / _band that met a request
+        self._nt_on = False        # pydisort.py: the corrections are switched on for the closures of the current call
+        self._idle_key = None      # pydisort.py: _plan_for, the shape under which the plan waits for a next call
         self.prep = prep
         self.C, self.L, self.N, self.Q = prep["C"], prep["L"], prep["N"], 2 * prep["N"]
         self.M = prep["M"]
@@ -67,10 +134,10 @@ class Plan:
         self.solved = False
 
     def _band_active(self):
-        return self.prep.get("band") is not None or getattr(self, "_band", None) is not None
+        return self.prep.get("band") is not None or self._band is not None
 
     def _band_allowed(self):
-        if getattr(self, "_sharded", False) or getattr(self, "_nranks", None) is not None:
+        if self._sharded or self._nranks is not None:
             raise ValueError("band inputs and band weights are not combined with a mode shard or a communicator.")
 
     def allreduce_results(self):
@@ -112,53 +179,52 @@ class Plan:
         names = ("tau_arr", "omega_arr", "leg", "f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "s_poly", "bdrf_q", "bdrf_q0")
         a = {k: _f64(raw.get(k)) for k in names}
         p = self.prep
-        Cn, L, N, M, Ns, NB = p["C"], p["L"], p["N"], p["M"], p["Ns"], p["NBDRF"]
-        want = {"tau_arr": (Cn, L), "omega_arr": (Cn, L), "f_arr": (Cn, L), "mu0": (Cn,), "I0": (Cn,), "phi0": (Cn,),
-                "b_pos": (Cn, M, N), "b_neg": (Cn, M, N), "s_poly": (Cn, L, Ns), "bdrf_q": (Cn, NB, N, N),
-                "bdrf_q0": (Cn, NB, N)}
-        required = {"tau_arr", "omega_arr", "f_arr", "mu0", "I0", "phi0"} | ({"s_poly"} if Ns > 0 and _thermal is None else set()) \
-            | ({"bdrf_q", "bdrf_q0"} if NB > 0 and not self._surface_requested() else set())
-        if self._surface_requested() and (a["bdrf_q"] is not None or a["bdrf_q0"] is not None):
-            raise ValueError("raw batch does not match the plan: a surface is requested, bdrf_q and bdrf_q0 must be None")
-        if a["leg"] is None or a["leg"].ndim != 3 or a["leg"].shape[:2] != (Cn, L) or a["leg"].shape[2] < p["P"]:
-            raise ValueError(f"raw batch does not match the plan: leg must be [C = {Cn}, L = {L}, nleg_all >= {p['P']}]")
-        for k, shape in want.items():
-            if a[k] is None:
-                if k in required:
-                    raise ValueError(f"raw batch does not match the plan: {k} is required")
-                continue
-            if (k == "s_poly" and Ns == 0) or (k.startswith("bdrf") and NB == 0):
-                a[k] = None  # the plan has no such term; the library ignores the pointer
-                continue
-            if a[k].shape != shape:
-                raise ValueError(f"raw batch does not match the plan: {k} has the shape {a[k].shape}, expected {shape}")
-        if not p["beam"] and np.any(a["I0"] > 0):
-            raise ValueError("raw batch has a beam source but the plan was created without one")
+        self._check_columns(a, {"tau_arr", "omega_arr", "f_arr", "mu0", "I0", "phi0"} | ({"s_poly"} if p["Ns"] > 0 and _thermal is None else set()), "raw")
         if _thermal is None:
             _lib.check(self._lib.rtd_plan_set_columns_raw(
                 self._h, _lib.dptr(a["tau_arr"]), _lib.dptr(a["omega_arr"]), _lib.dptr(a["leg"]), a["leg"].shape[2],
                 *[_lib.dptr(a[k]) for k in ("f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "s_poly", "bdrf_q", "bdrf_q0")]))
         else:
-            if Ns != 2 or a["s_poly"] is not None:
+            if p["Ns"] != 2 or a["s_poly"] is not None:
                 raise ValueError("thermal batch does not match the plan: it needs Ns = 2 and no s_poly")
-            twant = {"TEMPER": (Cn, L + 1), "WVNMLO": (Cn,), "WVNMHI": (Cn,), "BTEMP": (Cn,), "TTEMP": (Cn,), "TEMIS": (Cn,),
-                     "emissivity": (Cn, N)}
-            t = {k: _f64(_thermal.get(k)) for k in twant}
-            for k, shape in twant.items():
-                if t[k] is None:
-                    if k in ("TEMPER", "WVNMLO", "WVNMHI"):
-                        raise ValueError(f"thermal batch does not match the plan: {k} is required")
-                elif t[k].shape != shape:
-                    raise ValueError(f"thermal batch does not match the plan: {k} has the shape {t[k].shape}, expected {shape}")
-            th = _lib.rtd_thermal(*[_lib.dptr(t[k]) for k in ("TEMPER", "WVNMLO", "WVNMHI", "BTEMP", "TTEMP", "TEMIS", "emissivity")])
+            th, keep = _thermal_struct(_thermal, p["C"], p["L"], p["N"])
             _lib.check(self._lib.rtd_plan_set_columns_thermal(
                 self._h, _lib.dptr(a["tau_arr"]), _lib.dptr(a["omega_arr"]), _lib.dptr(a["leg"]), a["leg"].shape[2],
                 *[_lib.dptr(a[k]) for k in ("f_arr", "mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")], C.byref(th)))
         # what later checks (set_columns, the closures' tau range, beam terms) compare against follows the new batch
         self.prep = dict(p, tau=a["tau_arr"], mu0=a["mu0"], phi0=a["phi0"], raw=raw, thermal=_thermal, band=None)
-        if getattr(self, "_nt_request", 0):
+        if self._nt_request:
             self._nt_nleg_all = self._nt_request
         self.solved = False
+
+    def _check_columns(self, a, required, label):
+        """The per-column arrays `a` of a raw or band upload (name -> array, None: not given) against the shapes the plan implies;
+        `label`: "raw" or "band".  `required`: what must be given besides the BDRF tables, which are required when the plan has BDRF
+        modes and no surface is requested, and refused when one is.  An array of a term the plan does not have becomes None in `a`
+        (the library ignores the pointer).  "leg", where `a` has it, is [C, L, nleg_all >= NLeg]."""
+        p = self.prep
+        Cn, L, N, M, Ns, NB = p["C"], p["L"], p["N"], p["M"], p["Ns"], p["NBDRF"]
+        shapes = {"tau_arr": (Cn, L), "omega_arr": (Cn, L), "f_arr": (Cn, L), "mu0": (Cn,), "I0": (Cn,), "phi0": (Cn,),
+                  "b_pos": (Cn, M, N), "b_neg": (Cn, M, N), "s_poly": (Cn, L, Ns), "bdrf_q": (Cn, NB, N, N), "bdrf_q0": (Cn, NB, N)}
+        requested = self._surface is not None
+        if requested and (a["bdrf_q"] is not None or a["bdrf_q0"] is not None):
+            raise ValueError(f"{label} batch does not match the plan: a surface is requested, bdrf_q and bdrf_q0 must be None")
+        if "leg" in a and (a["leg"] is None or a["leg"].ndim != 3 or a["leg"].shape[:2] != (Cn, L) or a["leg"].shape[2] < p["P"]):
+            raise ValueError(f"{label} batch does not match the plan: leg must be [C = {Cn}, L = {L}, nleg_all >= {p['P']}]")
+        if NB > 0 and not requested:
+            required = required | {"bdrf_q", "bdrf_q0"}
+        for k, shape in shapes.items():
+            if k not in a:
+                continue
+            if a[k] is None:
+                if k in required:
+                    raise ValueError(f"{label} batch does not match the plan: {k} is required")
+            elif (k == "s_poly" and Ns == 0) or (k.startswith("bdrf") and NB == 0):
+                a[k] = None
+            elif a[k].shape != shape:
+                raise ValueError(f"{label} batch does not match the plan: {k} has the shape {a[k].shape}, expected {shape}")
+        if not p["beam"] and np.any(a["I0"] > 0):
+            raise ValueError(f"{label} batch has a beam source but the plan was created without one")
 
     def set_columns_band(self, band, cols, thermal=None):
         """Upload a batch of P profiles x G spectral points as a k-distribution band; tau_arr, omega_arr, f_arr and the moments of
@@ -169,7 +235,7 @@ class Plan:
         it.  The C ABI takes bare pointers whose extents the plan implies, so every array's shape is checked here."""
         self._band_allowed()
         p = self.prep
-        Cn, L, N, M, Ns, NB = p["C"], p["L"], p["N"], p["M"], p["Ns"], p["NBDRF"]
+        Cn, L, Ns = p["C"], p["L"], p["Ns"]
         b = {k: _f64(band.get(k)) for k in ("dtau_abs", "dtau_spec", "omega_spec", "leg_spec")}
         if any(v is None for v in b.values()) or b["dtau_abs"].ndim != 3 or b["dtau_spec"].ndim != 3 or b["leg_spec"].ndim != 2:
             raise ValueError("band does not match the plan: dtau_abs [P, G, L], dtau_spec and omega_spec [P, L, S] and leg_spec "
@@ -185,35 +251,13 @@ class Plan:
         if nleg_all < p["P"] + int(delta_m):
             raise ValueError(f"band does not match the plan: leg_spec needs {p['P'] + int(delta_m)} moments per species, has {nleg_all}")
         a = {k: _f64(cols.get(k)) for k in ("mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")}
-        want = {"mu0": (Cn,), "I0": (Cn,), "phi0": (Cn,), "b_pos": (Cn, M, N), "b_neg": (Cn, M, N), "bdrf_q": (Cn, NB, N, N),
-                "bdrf_q0": (Cn, NB, N)}
-        required = {"mu0", "I0", "phi0"} | ({"bdrf_q", "bdrf_q0"} if NB > 0 and not self._surface_requested() else set())
-        if self._surface_requested() and (a["bdrf_q"] is not None or a["bdrf_q0"] is not None):
-            raise ValueError("band batch does not match the plan: a surface is requested, bdrf_q and bdrf_q0 must be None")
-        for k, shape in want.items():
-            if a[k] is None:
-                if k in required:
-                    raise ValueError(f"band batch does not match the plan: {k} is required")
-            elif k.startswith("bdrf") and NB == 0:
-                a[k] = None
-            elif a[k].shape != shape:
-                raise ValueError(f"band batch does not match the plan: {k} has the shape {a[k].shape}, expected {shape}")
-        if not p["beam"] and np.any(a["I0"] > 0):
-            raise ValueError("band batch has a beam source but the plan was created without one")
+        self._check_columns(a, {"mu0", "I0", "phi0"}, "band")
         th, keep = None, None
         if thermal is not None:
             if Ns != 2:
                 raise ValueError("thermal batch does not match the plan: it needs Ns = 2")
-            twant = {"TEMPER": (Cn, L + 1), "WVNMLO": (Cn,), "WVNMHI": (Cn,), "BTEMP": (Cn,), "TTEMP": (Cn,), "TEMIS": (Cn,),
-                     "emissivity": (Cn, N)}
-            keep = {k: _f64(thermal.get(k)) for k in twant}
-            for k, shape in twant.items():
-                if keep[k] is None:
-                    if k in ("TEMPER", "WVNMLO", "WVNMHI"):
-                        raise ValueError(f"thermal batch does not match the plan: {k} is required")
-                elif keep[k].shape != shape:
-                    raise ValueError(f"thermal batch does not match the plan: {k} has the shape {keep[k].shape}, expected {shape}")
-            th = C.byref(_lib.rtd_thermal(*[_lib.dptr(keep[k]) for k in ("TEMPER", "WVNMLO", "WVNMHI", "BTEMP", "TTEMP", "TEMIS", "emissivity")]))
+            ts, keep = _thermal_struct(thermal, Cn, L, p["N"])
+            th = C.byref(ts)
         elif Ns != 0:
             raise ValueError("band batch does not match the plan: a plan with Ns > 0 needs thermal")
         bs = _lib.rtd_band(P, G, S, nleg_all, int(delta_m), *[_lib.dptr(b[k]) for k in ("dtau_abs", "dtau_spec", "omega_spec", "leg_spec")])
@@ -221,7 +265,7 @@ class Plan:
         _lib.check(self._lib.rtd_plan_set_columns_band(
             self._h, C.byref(bs), *[_lib.dptr(a[k]) for k in ("mu0", "I0", "phi0", "b_pos", "b_neg", "bdrf_q", "bdrf_q0")], th, _lib.dptr(tau)))
         self.prep = dict(p, tau=tau, mu0=a["mu0"], phi0=a["phi0"], band=band, cols=cols, thermal=thermal, raw=None)
-        if getattr(self, "_nt_request", 0):
+        if self._nt_request:
             self._nt_nleg_all = self._nt_request
         self.solved = False
         return tau
@@ -240,14 +284,18 @@ class Plan:
         _lib.check(self._lib.rtd_plan_set_band_weights(self._h, w.shape[1], w.shape[0], _lib.dptr(w)))
         self._band = (self.C // w.shape[1], w.shape[0])
 
-    def _band_arrays(self, ntau, nphi, want):
-        if getattr(self, "_band", None) is None:
-            raise ValueError("set_band_weights must precede fetch_band / evaluate_band.")
-        P, K = self._band
-        u = np.empty((P, K, self.Q, ntau, nphi)) if ("u" in want and nphi > 0) else None
-        u0 = np.empty((P, K, self.Q, ntau)) if "u0" in want else None
-        fl = [np.empty((P, K, ntau)) for _ in range(3)] if "flux" in want else [None] * 3
-        return dict(u=u, u0=u0, flux_up=fl[0], flux_down_diffuse=fl[1], flux_down_direct=fl[2])
+    @staticmethod
+    def _after(state, setter, caller):
+        """What `setter` left in the plan's `state`, for a `caller` that needs it; the refusal of one that came before it."""
+        if state is None:
+            raise ValueError(f"{setter} must precede {caller}.")
+        return state
+
+    def _stored_points(self, caller):
+        return self._after(self._ev_shape, "set_eval_points", caller)
+
+    def _band_shape(self, caller):
+        return self._after(self._band, "set_band_weights", caller)
 
     def _checked_band(self, rc):
         """The device has already written NaN into every profile with a failed column: numeric_errors == "nan" only has to keep
@@ -260,10 +308,9 @@ class Plan:
         (include/rtd.h: rtd_plan_fetch_band) -> dict(u [P, K, Q, ntau, nphi], u0 [P, K, Q, ntau], flux_up / flux_down_diffuse /
         flux_down_direct [P, K, ntau]); what `want` leaves out is neither reduced nor copied (None).  A profile with a failed
         column is NaN (numeric_errors == "nan") or raises NumericalError."""
-        ntau, nphi = self._ev_shape
-        out = self._band_arrays(ntau, nphi, want)
-        self._checked_band(self._lib.rtd_plan_fetch_band(
-            self._h, *[_lib.dptr(out[k]) for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")]))
+        ntau, nphi = self._stored_points("fetch_band")
+        out = _result_arrays(self._band_shape("fetch_band / evaluate_band"), self.Q, ntau, nphi, want)
+        self._checked_band(self._lib.rtd_plan_fetch_band(self._h, *_result_ptrs(out)))
         return out
 
     def evaluate_band(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
@@ -271,21 +318,10 @@ class Plan:
         be the same physical level), phi [nphi] or None -> the dict of ``fetch_band`` (include/rtd.h: rtd_plan_evaluate_band);
         "act" in `want` adds the reduced actinic fluxes of ``fetch_band_actinic``, "view" the reduced radiances at the angles of
         ``set_view`` (``fetch_band_view``; "view_u" / "view_u0": one of the two)."""
-        if antiderivative and derivative:
-            raise ValueError("antiderivative and derivative exclude each other.")
-        tau = _f64(np.atleast_2d(tau))
-        assert tau.shape[0] == self.C
-        ntau = tau.shape[1]
-        phi = _f64(np.atleast_1d(phi)) if phi is not None else None
-        nphi = 0 if phi is None else len(phi)
-        out = self._band_arrays(ntau, nphi, want)
+        tau, ntau, phi, nphi, flags, view = self._eval_args(tau, phi, antiderivative, derivative, skip_nt, want)
+        out = _result_arrays(self._band_shape("fetch_band / evaluate_band"), self.Q, ntau, nphi, want)
         self._ev_shape = (ntau, nphi)
-        view = self._view_want(want)
-        keep_u = 8 if ("u" in view and nphi > 0) else 0  # (u is formed on the device although nothing of it is copied)
-        self._checked_band(self._lib.rtd_plan_evaluate_band(
-            self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi),
-            int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0) | keep_u,
-            *[_lib.dptr(out[k]) for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")]))
+        self._checked_band(self._lib.rtd_plan_evaluate_band(self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi), flags, *_result_ptrs(out)))
         if "act" in want:
             out.update(self.fetch_band_actinic())
         if view:
@@ -298,9 +334,7 @@ class Plan:
         """Points per column of the results the plan holds now, as the plan itself reports it (include/rtd.h:
         rtd_plan_result_dev_ptrs, flux_bytes = 3 C ntau 8).  The host arrays of the actinic fetches are sized from this and from
         nothing this object remembers: evaluate() moves the plan's points without a fetch of the stored ones in mind."""
-        fb = C.c_int64()
-        _lib.check(self._lib.rtd_plan_result_dev_ptrs(self._h, None, None, None, C.byref(fb)))
-        return int(fb.value // (24 * self.C))
+        return self._resident_shape()[0]
 
     def fetch_actinic(self, out=None):
         """Actinic fluxes (4 pi x the mean intensity) of the results the plan holds -- after run(), run_fetch(), evaluate() or
@@ -309,16 +343,7 @@ class Plan:
         flux_act_down_diffuse, flux_act_down_direct [C, ntau]); diffuse + direct is the physical downward actinic flux.  `out`:
         dict whose arrays of those names are filled in place (C-contiguous float64 [C, ntau], anything else is a ValueError);
         the others are allocated."""
-        shape = (self.C, self._resident_ntau())
-        given = out or {}
-        out = {}
-        for k in self._ACT:
-            a = given.get(k)
-            if a is None:
-                a = np.empty(shape)
-            elif not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable and a.shape == shape):
-                raise ValueError(f"out[{k!r}] must be a writeable C-contiguous float64 array of the shape {shape}.")
-            out[k] = a
+        out = _out_arrays(out, dict.fromkeys(self._ACT, (self.C, self._resident_ntau())))
         self._checked(self._lib.rtd_plan_fetch_actinic(self._h, *[_lib.dptr(out[k]) for k in self._ACT]), out)
         return out
 
@@ -326,10 +351,8 @@ class Plan:
         """``fetch_actinic`` summed over the spectral points with every weight set on the device (include/rtd.h:
         rtd_plan_fetch_band_actinic) -> the same keys, [P, K, ntau].  With weights = cross section x quantum yield x k-weight the sum
         of the three is the photolysis rate per level."""
-        if getattr(self, "_band", None) is None:
-            raise ValueError("set_band_weights must precede fetch_band_actinic.")
-        P, K = self._band
-        out = {k: np.empty((P, K, self._resident_ntau())) for k in self._ACT}
+        shape = self._band_shape("fetch_band_actinic") + (self._resident_ntau(),)
+        out = {k: np.empty(shape) for k in self._ACT}
         self._checked_band(self._lib.rtd_plan_fetch_band_actinic(self._h, *[_lib.dptr(out[k]) for k in self._ACT]))
         return out
 
@@ -346,9 +369,8 @@ class Plan:
             self._view = None
             return
         mu = view_angles(mu, self.C)
-        band = getattr(self, "_band", None)
-        if mu.ndim == 2 and band is not None:
-            per_profile = mu.reshape(band[0], self.C // band[0], -1)
+        if mu.ndim == 2 and self._band is not None:
+            per_profile = mu.reshape(self._band[0], self.C // self._band[0], -1)
             if not np.array_equal(per_profile, np.broadcast_to(per_profile[:, :1], per_profile.shape)):
                 raise ValueError("mu must be the same for the columns of a band profile.")
         _lib.check(self._lib.rtd_plan_set_view_mu(self._h, mu.shape[-1], _lib.dptr(mu), int(mu.ndim == 2)))
@@ -365,24 +387,14 @@ class Plan:
     def _view_arrays(self, lead, want, out):
         """The host arrays of the two view fetches: `lead` + (nmu, ntau[, nphi]).  u_mu is None when "u" is not wanted or the
         resident results have no azimuths; arrays of `out` are checked and filled in place, the others allocated."""
-        if getattr(self, "_view", None) is None:
-            raise ValueError("set_view must precede fetch_view / fetch_band_view.")
+        nmu = self._after(self._view, "set_view", "fetch_view / fetch_band_view")
         ntau, nphi = self._resident_shape()
         shapes = {}
         if "u" in want and nphi > 0:
-            shapes["u_mu"] = lead + (self._view, ntau, nphi)
+            shapes["u_mu"] = lead + (nmu, ntau, nphi)
         if "u0" in want:
-            shapes["u0_mu"] = lead + (self._view, ntau)
-        given = out or {}
-        arrays = dict(u_mu=None, u0_mu=None)
-        for k, shape in shapes.items():
-            a = given.get(k)
-            if a is None:
-                a = np.empty(shape)
-            elif not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable and a.shape == shape):
-                raise ValueError(f"out[{k!r}] must be a writeable C-contiguous float64 array of the shape {shape}.")
-            arrays[k] = a
-        return arrays
+            shapes["u0_mu"] = lead + (nmu, ntau)
+        return dict(dict(u_mu=None, u0_mu=None), **_out_arrays(out, shapes))
 
     def fetch_view(self, want=("u", "u0"), out=None):
         """Radiances at the angles of ``set_view`` of the results the plan holds -- after run(), run_fetch(), evaluate() or
@@ -397,9 +409,7 @@ class Plan:
     def fetch_band_view(self, want=("u", "u0")):
         """``fetch_view`` summed over the spectral points with every weight set on the device (include/rtd.h:
         rtd_plan_fetch_band_view) -> dict(u_mu [P, K, nmu, ntau, nphi], u0_mu [P, K, nmu, ntau])."""
-        if getattr(self, "_band", None) is None:
-            raise ValueError("set_band_weights must precede fetch_band_view.")
-        arrays = self._view_arrays(tuple(self._band), want, None)
+        arrays = self._view_arrays(self._band_shape("fetch_band_view"), want, None)
         self._checked_band(self._lib.rtd_plan_fetch_band_view(self._h, _lib.dptr(arrays["u_mu"]), _lib.dptr(arrays["u0_mu"])))
         return arrays
 
@@ -409,6 +419,7 @@ class Plan:
         return tuple(k for k, names in (("u", ("view", "view_u")), ("u0", ("view", "view_u0"))) if any(n in want for n in names))
 
     def close(self):
+        # (probed, like nothing else of the plan's: __init__ can fail before the handle exists, and __del__ still comes here)
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.rtd_plan_destroy(self._h)
             self._h = None
@@ -452,9 +463,6 @@ class Plan:
         _lib.check(self._lib.rtd_plan_request_nt(self._h, int(nleg_all)))
         self._nt_request = max(int(nleg_all), 0)
 
-    def _surface_requested(self):
-        return getattr(self, "_surface", None) is not None
-
     def request_surface(self, model, params=None, nphi=256):
         """While a surface is requested, ``set_columns_raw`` / ``_thermal`` / ``_band`` form the plan's BDRF Fourier modes on the
         device from a parametric model instead of taking ``bdrf_q`` / ``bdrf_q0`` (include/rtd.h: rtd_plan_request_surface; the
@@ -493,6 +501,8 @@ class Plan:
         rows = C.c_int32()
         _lib.check(self._lib.rtd_plan_get_nt(self._h, None, None, None, None, C.byref(rows)))  # (RTD_ERR_STATE without NT)
         nall = self._nt_nleg_all  # (the call does not report it: that of the last upload, or of the request the columns met)
+        if not nall:
+            raise ValueError("set_nt or request_nt must precede get_nt.")
         out = dict(wfull=np.empty((rows.value, self.L, nall)), f=np.empty((self.C, self.L)), ims_coef=np.empty((self.C, nall)),
                    ims_par=np.empty((self.C, 2)))
         _lib.check(self._lib.rtd_plan_get_nt(self._h, *[_lib.dptr(out[k]) for k in ("wfull", "f", "ims_coef", "ims_par")], None))
@@ -506,23 +516,17 @@ class Plan:
         _lib.check(self._lib.rtd_plan_synchronize(self._h))
 
     def device_bytes(self):
-        b = C.c_int64()
-        _lib.check(self._lib.rtd_plan_device_bytes(self._h, C.byref(b)))
-        return b.value
+        return _out_int(self._lib.rtd_plan_device_bytes, self._h)
 
     @staticmethod
     def pool_bytes():
         """Device memory of closed plans that the library keeps for the next plan (include/rtd.h: rtd_pool_bytes)."""
-        b = C.c_int64()
-        _lib.check(_lib.load().rtd_pool_bytes(C.byref(b)))
-        return b.value
+        return _out_int(_lib.load().rtd_pool_bytes)
 
     @staticmethod
     def pool_trim(device=-1):
         """Gives that memory back to the runtime (include/rtd.h: rtd_pool_trim); returns the bytes released."""
-        b = C.c_int64()
-        _lib.check(_lib.load().rtd_pool_trim(int(device), C.byref(b)))
-        return b.value
+        return _out_int(_lib.load().rtd_pool_trim, int(device))
 
     @staticmethod
     def free_device_bytes(device=0):
@@ -535,9 +539,7 @@ class Plan:
     def pool_set_limit(nbytes=-1, device=0):
         """Opt in to (or out of) keeping the LARGE device blocks of closed plans for the next plan: nbytes per device, < 0 = an
         eighth of the device's memory, 0 = off (the default).  Returns the previous limit (include/rtd.h: rtd_pool_set_limit)."""
-        b = C.c_int64()
-        _lib.check(_lib.load().rtd_pool_set_limit(int(nbytes), int(device), C.byref(b)))
-        return b.value
+        return _out_int(_lib.load().rtd_pool_set_limit, int(nbytes), int(device))
 
     def evaluate(self, tau, phi=None, antiderivative=False, want=("u", "u0", "flux"), skip_nt=False, derivative=False):
         """tau [C, ntau]; phi [nphi] or None -> dict of arrays (u [C,Q,ntau,nphi], u0 [C,Q,ntau],
@@ -547,32 +549,37 @@ class Plan:
         unless "u" is wanted too).  derivative: every output is its
         derivative with respect to the unscaled tau (include/rtd.h: bit 2 of rtd_plan_evaluate's flag word; one-sided from above
         at an interface); not together with antiderivative."""
-        if antiderivative and derivative:
-            raise ValueError("antiderivative and derivative exclude each other.")
-        tau = _f64(np.atleast_2d(tau))
-        assert tau.shape[0] == self.C
-        ntau = tau.shape[1]
-        phi = _f64(np.atleast_1d(phi)) if phi is not None else None
-        nphi = 0 if phi is None else len(phi)
-        out = {}
-        u = np.empty((self.C, self.Q, ntau, nphi)) if ("u" in want and nphi > 0) else None
-        u0 = np.empty((self.C, self.Q, ntau)) if "u0" in want else None
-        ul = np.empty((self.C, self.Q, ntau)) if "ulast" in want else None
-        fl = [np.empty((self.C, ntau)) for _ in range(3)] if "flux" in want else [None] * 3
-        out.update(u=u, u0=u0, ulast=ul, flux_up=fl[0], flux_down_diffuse=fl[1], flux_down_direct=fl[2])
-        view = self._view_want(want)
-        keep_u = 8 if ("u" in view and nphi > 0) else 0  # (u is formed on the device although nothing of it is copied)
-        self._checked(self._lib.rtd_plan_evaluate(self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi),
-                                                  int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0) | keep_u,
-                                                  _lib.dptr(u),
-                                                  _lib.dptr(u0),
-                                                  _lib.dptr(fl[0]), _lib.dptr(fl[1]), _lib.dptr(fl[2]),
-                                                  _lib.dptr(ul)), out)
+        tau, ntau, phi, nphi, flags, view = self._eval_args(tau, phi, antiderivative, derivative, skip_nt, want)
+        # The arrays and their pointers are spelled out here, not taken from _result_arrays / _result_ptrs: this is the one call of
+        # the class that bench.py times per call (a whole one-column pydisort() with one closure), and through the helpers that
+        # call measured 5 to 7 us slower (HISTORY.md).
+        field, level, dptr = (self.C, self.Q, ntau), (self.C, ntau), _lib.dptr
+        u = np.empty(field + (nphi,)) if ("u" in want and nphi > 0) else None
+        u0 = np.empty(field) if "u0" in want else None
+        ul = np.empty(field) if "ulast" in want else None
+        fu, fd, fb = (np.empty(level), np.empty(level), np.empty(level)) if "flux" in want else (None, None, None)
+        out = dict(u=u, u0=u0, ulast=ul, flux_up=fu, flux_down_diffuse=fd, flux_down_direct=fb)
+        self._checked(self._lib.rtd_plan_evaluate(self._h, ntau, dptr(tau), nphi, dptr(phi), flags, dptr(u), dptr(u0), dptr(fu), dptr(fd),
+                                                  dptr(fb), dptr(ul)), out)
         if "act" in want:
             out.update(self.fetch_actinic())
         if view:
             out.update(self.fetch_view(view))
         return out
+
+    def _eval_args(self, tau, phi, antiderivative, derivative, skip_nt, want):
+        """The arguments ``evaluate`` and ``evaluate_band`` share -> (tau [C, ntau], ntau, phi [nphi] or None, nphi, the flag word of
+        include/rtd.h: bit 0 antiderivative | 2 skip_nt | 4 derivative | 8 keep u on the device for the view, the `want` of the view
+        fetch)."""
+        if antiderivative and derivative:
+            raise ValueError("antiderivative and derivative exclude each other.")
+        tau = _f64(np.atleast_2d(tau))
+        assert tau.shape[0] == self.C
+        phi = _f64(np.atleast_1d(phi)) if phi is not None else None
+        nphi = 0 if phi is None else len(phi)
+        view = self._view_want(want)
+        keep_u = 8 if ("u" in view and nphi > 0) else 0  # (u is formed on the device although nothing of it is copied)
+        return tau, tau.shape[1], phi, nphi, int(bool(antiderivative)) | (2 if skip_nt else 0) | (4 if derivative else 0) | keep_u, view
 
     # ---- throughput form (results stay in HBM until fetch) ----
     def set_eval_points(self, tau, phi):
@@ -600,17 +607,13 @@ class Plan:
 
     def retained(self):
         """True when evaluate() after a solve only evaluates (one window, or the evaluator state of every column is resident)."""
-        r = C.c_int32()
-        _lib.check(self._lib.rtd_plan_retained(self._h, C.byref(r)))
-        return bool(r.value)
+        return self.retained_form() is not None
 
     def retained_form(self):
         """"full" (one window, or everything the evaluators read is resident for every column), "lean" (coefficients, k, E, B
         resident; evaluate() re-runs the eigen stage for the layers its points touch, never the boundary-condition solve) or
         None (evaluate() solves the windows again)."""
-        r = C.c_int32()
-        _lib.check(self._lib.rtd_plan_retained(self._h, C.byref(r)))
-        return {0: None, 1: "full", 2: "lean"}[r.value]
+        return {0: None, 1: "full", 2: "lean"}[_out_int(self._lib.rtd_plan_retained, self._h, ctype=C.c_int32)]
 
     def windows(self):
         """(columns per window, number of windows) of the plan's work arena."""
@@ -622,23 +625,16 @@ class Plan:
         """run() and fetch() as one host-to-host pipeline (device-to-host copies of a window overlap the next window's
         kernels; include/rtd.h: rtd_plan_run_fetch).  `out`: dict of preallocated arrays to fill (u, u0, flux_up,
         flux_down_diffuse, flux_down_direct; missing keys are not fetched), default: all of them, freshly allocated."""
-        ntau, nphi = self._ev_shape
+        ntau, nphi = self._stored_points("run_fetch")
         if out is None:
-            out = dict(u=np.empty((self.C, self.Q, ntau, nphi)), u0=np.empty((self.C, self.Q, ntau)),
-                       flux_up=np.empty((self.C, ntau)), flux_down_diffuse=np.empty((self.C, ntau)),
-                       flux_down_direct=np.empty((self.C, ntau)))
-        keys = ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")
-        self._checked(self._lib.rtd_plan_run_fetch(self._h, *[_lib.dptr(out.get(k)) for k in keys]), out)
+            out = _result_arrays((self.C,), self.Q, ntau, nphi)
+        self._checked(self._lib.rtd_plan_run_fetch(self._h, *_result_ptrs(out)), out)
         self.solved = True
         return out
 
     def fetch(self):
-        ntau, nphi = self._ev_shape
-        u = np.empty((self.C, self.Q, ntau, nphi))
-        u0 = np.empty((self.C, self.Q, ntau))
-        fl = [np.empty((self.C, ntau)) for _ in range(3)]
-        out = dict(u=u, u0=u0, flux_up=fl[0], flux_down_diffuse=fl[1], flux_down_direct=fl[2])
-        self._checked(self._lib.rtd_plan_fetch(self._h, _lib.dptr(u), _lib.dptr(u0), *[_lib.dptr(a) for a in fl]), out)
+        out = _result_arrays((self.C,), self.Q, *self._stored_points("fetch"))
+        self._checked(self._lib.rtd_plan_fetch(self._h, *_result_ptrs(out)), out)
         return out
 
     def result_dev_ptrs(self):
@@ -716,23 +712,23 @@ class Plan:
 
     def fetch_gathered_results(self, want_u=True):
         """-> (u [nranks * C, Q, ntau, nphi] or None, fluxes [nranks, 3, C, ntau]) of the last allgather_results()."""
-        ntau, nphi = self._ev_shape
-        u = np.empty((self._nranks * self.C, self.Q, ntau, nphi)) if want_u else None
-        fl = np.empty((self._nranks, 3, self.C, ntau))
+        (ntau, nphi), nranks = self._stored_points("fetch_gathered_results"), self._after(self._nranks, "comm_init", "fetch_gathered_results")
+        u = np.empty((nranks * self.C, self.Q, ntau, nphi)) if want_u else None
+        fl = np.empty((nranks, 3, self.C, ntau))
         _lib.check(self._lib.rtd_comm_fetch_gathered_results(self._h, _lib.dptr(u), _lib.dptr(fl)))
         return u, fl
 
     def fetch_gathered_columns(self, rank, first, count, want_u=True):
         """-> (u [count, Q, ntau, nphi] or None, fluxes [3, count, ntau]): the columns [first, first + count) of rank
         `rank`'s shard in the gathered arrays of the last allgather_results() / gather_results()."""
-        ntau, nphi = self._ev_shape
+        ntau, nphi = self._stored_points("fetch_gathered_columns")
         u = np.empty((count, self.Q, ntau, nphi)) if want_u else None
         fl = np.empty((3, count, ntau))
         _lib.check(self._lib.rtd_comm_fetch_gathered_columns(self._h, int(rank), int(first), int(count), _lib.dptr(u), _lib.dptr(fl)))
         return u, fl
 
     def fetch_gathered(self):
-        out = np.empty((self._nranks, 3, self.C, self._ev_shape[0]))
+        out = np.empty((self._after(self._nranks, "comm_init", "fetch_gathered"), 3, self.C, self._stored_points("fetch_gathered")[0]))
         _lib.check(self._lib.rtd_comm_fetch_gathered(self._h, _lib.dptr(out)))
         return out
 
@@ -748,9 +744,7 @@ class Plan:
 
     def pivoted_chains(self):
         """(column, mode) chains of the last window that the tiled 64-stream BC kernel handed to the pivoted kernels."""
-        n = C.c_int32()
-        _lib.check(self._lib.rtd_plan_pivoted_chains(self._h, C.byref(n)))
-        return n.value
+        return _out_int(self._lib.rtd_plan_pivoted_chains, self._h, ctype=C.c_int32)
 
     # ---- a failed column in a batch: raise (default) or mark ----
     numeric_errors = "raise"  # or "nan": fill the failed columns of the returned arrays with NaN instead of raising
@@ -776,9 +770,7 @@ class Plan:
         return out
 
     def max_sweeps(self):
-        s = C.c_int32()
-        _lib.check(self._lib.rtd_plan_max_sweeps(self._h, C.byref(s)))
-        return s.value
+        return _out_int(self._lib.rtd_plan_max_sweeps, self._h, ctype=C.c_int32)
 
 
 def planck_band(T, WVNMLO, WVNMHI, device=0):
@@ -847,11 +839,9 @@ def solve_batch_once(prep, tau, phi, device=0):
     s, keep = _inputs_struct(prep)
     dims = _dims(prep)
     tau, phi = _f64(np.atleast_2d(tau)), _f64(np.atleast_1d(phi))
-    Cn, Q, nt, nph = prep["C"], 2 * prep["N"], tau.shape[1], phi.shape[0]
-    out = dict(u=np.empty((Cn, Q, nt, nph)), u0=np.empty((Cn, Q, nt)), flux_up=np.empty((Cn, nt)),
-               flux_down_diffuse=np.empty((Cn, nt)), flux_down_direct=np.empty((Cn, nt)))
-    _lib.check(lib.rtd_solve_batch(C.byref(dims), device, C.byref(s), nt, _lib.dptr(tau), nph, _lib.dptr(phi),
-                                   *[_lib.dptr(out[k]) for k in ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")]))
+    nt, nph = tau.shape[1], phi.shape[0]
+    out = _result_arrays((prep["C"],), 2 * prep["N"], nt, nph)
+    _lib.check(lib.rtd_solve_batch(C.byref(dims), device, C.byref(s), nt, _lib.dptr(tau), nph, _lib.dptr(phi), *_result_ptrs(out)))
     return out
 
 

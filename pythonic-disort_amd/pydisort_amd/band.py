@@ -10,7 +10,7 @@ import numpy as np
 
 from ._engine import Plan, view_angles
 from ._prepare import double_gauss
-from .batch import BatchSolution, _nt_checks, _retention, _thermal_inputs
+from .batch import BatchSolution, _check_numeric_errors, _default_window, _nt_checks, _retention, _stream_counts, _thermal_inputs
 from ._surface import surface_request
 
 
@@ -64,13 +64,7 @@ def _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0
         raise ValueError(f"omega_spec must have the shape of dtau_spec {(P, L, S)}.")
     if leg.ndim != 2 or leg.shape[0] != S:
         raise ValueError(f"Leg_spec must have the shape [S = {S}, NLeg_all].")
-    N = NQuad // 2
-    NLeg = NQuad if NLeg is None else NLeg
-    NFourier = 1 if only_flux else (NQuad if NFourier is None else NFourier)
-    if NQuad % 2 or NQuad < 2 or NQuad > 128:
-        raise ValueError("NQuad must be even and between 2 and 128.")
-    if not (0 < NFourier <= NLeg <= NQuad and NLeg <= leg.shape[1]):
-        raise ValueError("Need 0 < NFourier <= NLeg <= NQuad and NLeg <= number of Legendre coefficients provided.")
+    N, NLeg, NFourier = _stream_counts(NQuad, NLeg, NFourier, only_flux, leg.shape[1])
     if delta_M and leg.shape[1] <= NLeg:
         raise ValueError("delta_M needs more Legendre coefficients per species than NLeg (the truncation fraction is moment NLeg).")
     if not (np.all(a >= 0) and np.all(ds >= 0)):
@@ -262,8 +256,7 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
     Returns (mu_arr, BandSolution)."""
     prep, w, squeeze = _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg, NFourier, delta_M,
                                     only_flux, b_pos, b_neg, bdrf_q, bdrf_q0, thermal, surface, NBDRF)
-    if numeric_errors not in ("raise", "nan"):
-        raise ValueError('numeric_errors must be "raise" or "nan".')
+    _check_numeric_errors(numeric_errors)
     if NT_cor and not only_flux:
         if not delta_M:
             raise ValueError("NT_cor needs delta_M: the corrections restore what the truncation removes.")
@@ -298,9 +291,8 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
     (``BandSolution.u_at``, ``Plan.fetch_band_view``).  surface, NBDRF as in ``pydisort_band``."""
     if mu is not None:
         mu = view_angles(mu, np.shape(dtau_abs)[0] if np.ndim(dtau_abs) == 3 else 0, "P")
-    if chunk_columns <= 0:  # (as solve_columns_streamed: windows of ~8 192 (column, mode) chains)
-        modes = 1 if only_flux else int(NFourier or NLeg or NQuad)
-        chunk_columns = max(64, 8192 // max(modes, 1))
+    if chunk_columns <= 0:
+        chunk_columns = _default_window(only_flux, NFourier, NLeg, NQuad)
     _, sol = pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=NLeg, NFourier=NFourier,
                            delta_M=delta_M, only_flux=only_flux, b_pos=b_pos, b_neg=b_neg, bdrf_q=bdrf_q, bdrf_q0=bdrf_q0,
                            thermal=thermal, device=device, work_columns=chunk_columns, numeric_errors=numeric_errors, retain=False,

@@ -68,6 +68,32 @@ def _nt_checks(I0, mu0, N, NLeg, nleg_all):
         raise ValueError("Some quadrature angles come too close to `mu0`. Perturb `NQuad` or `mu0` to rectify this error.")
 
 
+def _stream_counts(NQuad, NLeg, NFourier, only_flux, nleg_all):
+    """The defaults and rules of NQuad, NLeg and NFourier that ``pydisort_batch`` and ``pydisort_band`` share; nleg_all: the number
+    of Legendre coefficients provided -> (N, NLeg, NFourier)."""
+    NLeg = NQuad if NLeg is None else NLeg
+    NFourier = 1 if only_flux else (NQuad if NFourier is None else NFourier)
+    if NQuad % 2 or NQuad < 2 or NQuad > 128:
+        raise ValueError("NQuad must be even and between 2 and 128.")
+    if not (0 < NFourier <= NLeg <= NQuad and NLeg <= nleg_all):
+        raise ValueError("Need 0 < NFourier <= NLeg <= NQuad and NLeg <= number of Legendre coefficients provided.")
+    return NQuad // 2, NLeg, NFourier
+
+
+def _check_numeric_errors(numeric_errors):
+    if numeric_errors not in ("raise", "nan"):
+        raise ValueError('numeric_errors must be "raise" or "nan".')
+
+
+def _default_window(only_flux, NFourier, NLeg, NQuad):
+    """Columns per window of the streamed forms when the caller names none: windows of ~8 192 (column, mode) chains -- the two-stream
+    window pipeline of the library does best there (256 cfg4 columns: +4 % over windows of 2 048); the library
+    shrinks a window that does not fit the device (RTD_WORK_BYTES when set, else 80 % of the free device memory: rtd_api.hip
+    plan_build)."""
+    modes = 1 if only_flux else int(NFourier or NLeg or NQuad)
+    return max(64, 8192 // max(modes, 1))
+
+
 def _retention(retain, retain_bytes, defer_solve, C, N, NFourier, L, device):
     """``retain`` / ``retain_bytes`` of ``pydisort_batch`` -> (form, budget in bytes) for ``Plan``."""
     form = {"auto": 0, True: 0, "full": 1, "lean": 2}.get(retain if isinstance(retain, (str, bool)) else "auto")
@@ -116,38 +142,40 @@ class BatchSolution:
             raise ValueError("`is_derivative_wrt_tau` and `is_antiderivative_wrt_tau` cannot both be set.")
         return bool(is_derivative_wrt_tau)
 
+    def _eval(self, want, tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu=None):
+        """One device evaluation of `want` for an evaluator: the order's check, then the view angles `mu` (``u_at`` / ``u0_at``), then
+        the range check of tau -> the dict of ``Plan.evaluate``."""
+        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        if mu is not None:
+            self.plan.set_view(mu)
+        return self.plan.evaluate(self._tau(tau), phi, is_antiderivative_wrt_tau, want=(want,), derivative=deriv)
+
     def u(self, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> [C, NQuad, ntau, nphi]"""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        return self.plan.evaluate(self._tau(tau), phi, is_antiderivative_wrt_tau, want=("u",), derivative=deriv)["u"]
+        return self._eval("u", tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["u"]
 
     def u0(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> [C, NQuad, ntau]"""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("u0",), derivative=deriv)["u0"]
+        return self._eval("u0", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["u0"]
 
     def flux_up(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> [C, ntau]"""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)["flux_up"]
+        return self._eval("flux", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["flux_up"]
 
     def flux_down(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """-> (diffuse [C, ntau], direct [C, ntau])"""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        r = self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)
+        r = self._eval("flux", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         return r["flux_down_diffuse"], r["flux_down_direct"]
 
     def flux_act_up(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """Upward actinic flux 2 pi sum_i w_i u0_i, formed on the device -> [C, ntau]"""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("act",), derivative=deriv)["flux_act_up"]
+        return self._eval("act", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["flux_act_up"]
 
     def flux_act_down(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """Downward actinic flux -> (diffuse [C, ntau], direct [C, ntau]).  The diffuse part carries the reference's delta-M
         reclassification term I0 e^(-tau* / mu0) - I0 e^(-tau / mu0) with the caller's I0 (``generate_diff_act_flux_funcs``); the
         direct part is flux_down_direct / mu0; their sum is the physical downward actinic flux."""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        r = self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("act",), derivative=deriv)
+        r = self._eval("act", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         return r["flux_act_down_diffuse"], r["flux_act_down_direct"]
 
     def u_at(self, mu, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
@@ -155,15 +183,11 @@ class BatchSolution:
         for the whole batch on the device -- barycentric polynomial interpolation in mu of the evaluated (Nakajima-Tanaka corrected)
         u, each hemisphere on its own; mu > 0 looks up, every other mu, 0 included, down (``Plan.set_view``).  Only u_mu leaves the
         device."""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        self.plan.set_view(mu)
-        return self.plan.evaluate(self._tau(tau), phi, is_antiderivative_wrt_tau, want=("view_u",), derivative=deriv)["u_mu"]
+        return self._eval("view_u", tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu)["u_mu"]
 
     def u0_at(self, mu, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """The azimuthal mean u0 at the polar-angle cosines mu [nmu] or [C, nmu] -> [C, nmu, ntau] (``u_at``)."""
-        deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
-        self.plan.set_view(mu)
-        return self.plan.evaluate(self._tau(tau), None, is_antiderivative_wrt_tau, want=("view_u0",), derivative=deriv)["u0_mu"]
+        return self._eval("view_u0", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu)["u0_mu"]
 
 
 def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLeg=None, NFourier=None,
@@ -225,13 +249,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
     Leg = np.asarray(Leg_coeffs_all, float)
     if Leg.ndim == 2:
         Leg = np.broadcast_to(Leg[None], (C,) + Leg.shape)
-    N = NQuad // 2
-    NLeg = NQuad if NLeg is None else NLeg
-    NFourier = 1 if only_flux else (NQuad if NFourier is None else NFourier)
-    if NQuad % 2 or NQuad < 2 or NQuad > 128:
-        raise ValueError("NQuad must be even and between 2 and 128.")
-    if not (0 < NFourier <= NLeg <= NQuad and NLeg <= Leg.shape[2]):
-        raise ValueError("Need 0 < NFourier <= NLeg <= NQuad and NLeg <= number of Legendre coefficients provided.")
+    N, NLeg, NFourier = _stream_counts(NQuad, NLeg, NFourier, only_flux, Leg.shape[2])
     if not (np.all(tau_arr > 0) and np.all(np.diff(tau_arr, axis=1) > 0)):
         raise ValueError("tau values must be positive and increasing.")
     if not (np.all(omega_arr >= 0) and np.all(omega_arr < 1)):
@@ -314,8 +332,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
         prep["M"] = len(modes)
         prep["mode_shard"] = (r, G, NFourier)
         NT_cor = NT_cor and r == 0
-    if numeric_errors not in ("raise", "nan"):
-        raise ValueError('numeric_errors must be "raise" or "nan".')
+    _check_numeric_errors(numeric_errors)
     form, budget = _retention(retain, retain_bytes, _defer_solve, C, N, NFourier, L, device)
     plan = Plan(prep, device=device, work_columns=work_columns, retain_bytes=budget, retain_form=form or 0)
     plan.numeric_errors = numeric_errors
@@ -368,12 +385,7 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
     if mu is not None:
         mu = view_angles(mu, C)
     if chunk_columns <= 0:
-        # windows of ~8 192 (column, mode) chains: the two-stream window pipeline of the library does best there (256 cfg4
-        # columns: +4 % over windows of 2 048); the library shrinks a window that does not fit the
-        # device (RTD_WORK_BYTES when set, else 80 % of the free device memory: rtd_api.hip plan_build)
-        nq = int(cfg["NQuad"])
-        modes = 1 if only_flux else int(cfg.get("NFourier") or cfg.get("NLeg") or nq)
-        chunk_columns = max(64, 8192 // max(modes, 1))
+        chunk_columns = _default_window(only_flux, cfg.get("NFourier"), cfg.get("NLeg"), int(cfg["NQuad"]))
     _, sol = pydisort_batch(only_flux=only_flux, device=device, work_columns=chunk_columns, device_prepare=True,
                             numeric_errors=numeric_errors, _defer_solve=True, **cfg)
     plan = sol.plan

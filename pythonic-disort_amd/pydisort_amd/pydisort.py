@@ -38,9 +38,9 @@ def _plan_for(prep, device):
                 _IDLE_COUNT[0] -= 1
         if plan is None:
             break
-        if getattr(plan, "_h", None):
+        if getattr(plan, "_h", None):  # (probed here and in _release: a plan whose constructor failed has no handle attribute)
             try:
-                if getattr(plan, "_nt_on", False):
+                if plan._nt_on:
                     plan.clear_nt()
                     plan._nt_on = False
                 plan.set_columns(prep)  # (same dimensions, same quadrature: only the column changes)
@@ -56,7 +56,7 @@ def _release(plan):
     """Called when the closures of a call are gone: the plan waits for the next call of its shape, or is closed."""
     if not getattr(plan, "_h", None):
         return
-    key = getattr(plan, "_idle_key", None)
+    key = plan._idle_key
     if key is not None:
         with _IDLE_LOCK:
             lst = _IDLE.get(key)

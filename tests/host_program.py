@@ -25,6 +25,18 @@ def build(tmp_path, main, name, defines=(), api=API):
     return exe
 
 
+def build_trace_library(tmp_path, name="librtd_trace.so"):
+    """rtd_api.hip + the shadow launchers as a plain shared library that logs its runtime calls (-DFAKE_HIP_TRACE) and that the
+    Python front end loads through RTD_LIB; no sanitizer, so a Python process needs nothing preloaded.  Skips the test without g++."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    lib = str(tmp_path / name)
+    subprocess.run([gxx, "-std=c++17", "-O1", "-fPIC", "-shared", "-Wno-unused-result", "-DFAKE_HIP_TRACE", "-I", os.path.join(CPU, "fake_hip"),
+                    "-x", "c++", API, os.path.join(CPU, "host_asan_shadow.cpp"), "-o", lib, "-ldl", "-lpthread"], check=True)
+    return lib
+
+
 def run(exe, *args):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                FAKE_HIP_TOTAL=str(8 << 30))
