@@ -448,6 +448,26 @@ int rtd_plan_fetch_band_actinic(rtd_plan* plan, double* act_up, double* act_down
  * weights; the call itself touches the host only.  Under band weights per-column angles must be identical within a profile
  * (RTD_ERR_ARG here when the weights are present, else from rtd_plan_fetch_band_view). */
 int rtd_plan_set_view_mu(rtd_plan* plan, int32_t nmu, const double* mu, int32_t per_column);
+/* Where the Nakajima-Tanaka corrections of the view of u come from.  mode 0 (default): from the interpolation, as above -- the
+ * corrected u of the nodes is interpolated.  That is right for the smooth delta-M solution and wrong in kind for the corrections: TMS
+ * is the single-scattering term of the full, untruncated phase function, whose forward peak a polynomial through the nodes cannot
+ * carry.  mode 1: the corrections are closed forms of the inputs and of (mu, tau, phi), so they are evaluated AT the angles
+ * (csrc/rtd_nt_view.hip, arithmetic csrc/rtd_nt_view.h):
+ *   u_mu(c, mu, tau, phi) = sum_j l_j(|mu|) u_uncorrected(c, j, tau, phi) + rescale_c [TMS + IMS](c, mu, tau, phi)
+ * TMS for both hemispheres, IMS for mu < 0 only, as at the nodes; in all three tau-orders.  The formulas are written so that they stay
+ * finite and keep their digits where the node formulas are infinity times zero: |mu| = mu0 (an almucantar has mu = -mu0 exactly),
+ * |mu| = the IMS scaled mu0 (ims_par[0]) and their neighbourhoods, and mu = +-1.  mu = +-0.0 is REFUSED in this mode (RTD_ERR_ARG, from
+ * this call when the held angles contain it, from rtd_plan_set_view_mu afterwards): the limit differs by hemisphere; mode 0 keeps
+ * accepting it.  u0_mu is untouched (the corrections never touched u0), and so are u, u0 and the fluxes themselves.
+ * The view of u is then formed BY THE EVALUATION (run, run_fetch, evaluate, evaluate_band), window by window, and the two fetches copy
+ * or reduce it as it is: angles or a mode set AFTER an evaluation leave the view of u unavailable until the next one (RTD_ERR_STATE
+ * from the fetches; u0_mu is still served).  Each output is one chain of additions in a fixed order, without atomics: the bits depend on
+ * neither the launch geometry nor the window size.  A plan without corrections, and an evaluation that skips them (bit 1 of the flag
+ * word), ignore the mode: their u is interpolated at the fetch.  Mode shards follow the node corrections' rule: the corrections are
+ * applied by whichever shard's plan has them switched on (the front end switches them on in the shard that owns mode 0 only), that
+ * shard's view carries them whole, and the shards' views add up.  With mode 0 every result of every entry point keeps its bits, and a
+ * plan that never asks for mode 1 allocates and launches nothing more.  RTD_ERR_ARG for any other mode.  Host only, sticky. */
+int rtd_plan_set_view_nt(rtd_plan* plan, int32_t mode);
 /* u_mu [C][nmu][ntau][nphi], u0_mu [C][nmu][ntau] of the LATEST evaluation (run, run_fetch, evaluate, evaluate_band), interpolated
  * on the plan's stream and copied out; either pointer may be NULL.  RTD_ERR_STATE when no angles are set, when the plan holds no
  * evaluated results (as rtd_plan_fetch_actinic), or when u_mu is asked for but the latest evaluation formed no u (nphi = 0, or an

@@ -25,6 +25,8 @@
 // by thread on heap memory, and replaces the other units by shadow launchers.  The ocean's mode kernel joins this unit there (one
 // lane per pair of cosines, no cross-lane step), so its indexing and every table it writes are bounds-checked and checked by value.
 #include "rtd_surface_ocean.hip"
+// likewise the corrections at the viewing angles (one thread per (column, angle) / per output, no cross-lane step)
+#include "rtd_nt_view.hip"
 #endif
 
 namespace {
@@ -343,6 +345,15 @@ struct rtd_plan {
   bool view_per_column = false, view_stale = true, res_has_u = false;
   std::vector<double> view_mu_h, h_mu_pos;
   DevBuf view_mu, view_b, view_l, view_flag, ev_view_u, ev_view_u0, rb_view_u, rb_view_u0;
+  // Corrections at the viewing angles themselves (rtd_plan_set_view_nt, rtd_nt_view.hip).  In mode 1 an evaluation that applies the
+  // Nakajima-Tanaka corrections forms the view of u ITSELF, window by window (launch_windows): the interpolant of the uncorrected u into
+  // ev_view_u, then the corrections at the angles on top; the fetches copy or reduce ev_view_u as it is.  res_nt: the latest evaluation
+  // applied the corrections to u; view_u_resident: it also left the view of u in ev_view_u and neither the angles nor the mode have
+  // changed since.  ntv_T [Cw][L][nmu]: the other-layer sums of one window, grown by the first such evaluation -- a plan that never asks
+  // holds and launches nothing more.
+  int view_nt_mode = 0;
+  bool res_nt = false, view_u_resident = false;
+  DevBuf ntv_T;
   // export buffers
   double* ex_buf = nullptr;
   // Nakajima-Tanaka corrections (optional)
@@ -432,6 +443,12 @@ struct rtd_plan {
     return 0;
   }
 };
+
+// the view's basis and its apply launch (defined with the view entry points; launch_windows queues them in rtd_plan_set_view_nt's mode 1)
+extern "C" {  // (the linkage of the block they are defined in)
+static int view_basis_queued(rtd_plan* p);
+static int view_apply_queued(rtd_plan* p, const double* X, int64_t E, int64_t c0, int64_t cnt, double* out);
+}
 
 namespace {
 
@@ -574,6 +591,16 @@ RtdNt window_nt(const rtd_plan* p, int64_t c0) {
   w.R += c0 * 4 * p->d.NP * L;
   return w;
 }
+// the window's angles, its slice of the view of u (E doubles per column and angle) and the one-window table of the other-layer sums
+RtdNtView window_nt_view(const rtd_plan* p, int64_t c0, int64_t E) {
+  RtdNtView v{};
+  v.nmu = p->view_nmu;
+  v.mu_stride = p->view_per_column ? p->view_nmu : 0;
+  v.mu = p->view_mu + c0 * v.mu_stride;
+  v.T = p->ntv_T;
+  v.out = p->ev_view_u + c0 * p->view_nmu * E;
+  return v;
+}
 
 // Lean retained plans: which wavefront chunks of the eigen stage the evaluation points of a column touch.  One thread per
 // column: the layer of every point exactly as the evaluation kernel finds it (rtd_eval.hip: argmax(tau <= tau_arr),
@@ -614,6 +641,19 @@ int launch_windows(rtd_plan* p, bool with_solve, const RtdEval* ev, bool with_nt
   const bool pipe = p->pipelined && with_solve && !tm && p->nwin > 1;
   hipStream_t se = pipe ? p->eig_stream : s;
   bool nt_tables_done = false;
+  // Corrections at the viewing angles (rtd_plan_set_view_nt, mode 1): this pass forms the view of u itself.  Per window, behind the
+  // evaluation kernel: the interpolant of the UNCORRECTED u into the window's slice of ev_view_u; then the node corrections, as ever,
+  // so that u keeps its bits; then the corrections at the angles on the slice (rtd_nt_view.hip).  A plan without corrections, an
+  // evaluation that skips them or forms no u, and mode 0 queue nothing of this: the fetch interpolates the resident u, as before.
+  const bool view_nt = ev && ev->u && with_nt && p->view_nt_mode == 1 && p->view_nmu > 0;
+  if (ev) p->view_u_resident = false;
+  if (view_nt) {
+    const ResultShape r(p);
+    int rc;
+    if ((rc = view_basis_queued(p)) || (rc = grow(p, p->ev_view_u, r.C * p->view_nmu * r.nt * r.np)) ||
+        (rc = grow(p, p->ntv_T, (int64_t)p->Cw * p->d.L * p->view_nmu)))
+      return rc;
+  }
   if (pipe && p->fork_needed) {  // the eigen stream starts behind the uploads queued on the plan's stream; without new inputs
     //                              it only waits, slot by slot, for the consumers of the previous run (ev_bc below), so that
     //                              back-to-back runs keep the pipeline full
@@ -721,6 +761,11 @@ int launch_windows(rtd_plan* p, bool with_solve, const RtdEval* ev, bool with_nt
       RtdEval e = window_eval(p, *ev, c0);
       e.um_in = fused ? p->um_buf.p : nullptr;
       rtd_launch_eval(d, e, s);
+      const int64_t Eu = (int64_t)e.ntau * e.nphi;
+      if (view_nt) {
+        int rc = view_apply_queued(p, e.u, Eu, c0, cnt, p->ev_view_u);
+        if (rc) return rc;
+      }
       if (with_nt && e.u != nullptr) {
         const RtdNt nt = window_nt(p, c0);
         if (!p->nt_tables_ready) {
@@ -728,6 +773,11 @@ int launch_windows(rtd_plan* p, bool with_solve, const RtdEval* ev, bool with_nt
           nt_tables_done = true;
         }
         rtd_launch_nt_apply(d, nt, e, s);
+        if (view_nt) {
+          const RtdNtView v = window_nt_view(p, c0, Eu);
+          rtd_launch_nt_view_tables(d, v, e.antider, s);
+          rtd_launch_nt_view_apply(d, nt, e, v, s);
+        }
       }
       mark(7);
     }
@@ -745,6 +795,10 @@ int launch_windows(rtd_plan* p, bool with_solve, const RtdEval* ev, bool with_nt
     if (rc) return rc;
   }
   if (nt_tables_done) p->nt_tables_ready = true;  // every window's tables were made in this pass
+  if (ev) {
+    p->res_nt = with_nt && ev->u != nullptr;
+    p->view_u_resident = view_nt;
+  }
   if (with_solve) p->solved = true;
   if (with_solve && !pipe) p->fork_needed = true;  // slot 0 was filled on the plan's own stream
   return 0;
@@ -800,7 +854,7 @@ extern "C" {
 
 int rtd_comm_destroy(rtd_plan* p);
 
-int rtd_version(void) { return 217; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt; 216: rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view, bit 3 of the evaluation flag word; 217: rtd_plan_request_surface, rtd_surface_samples, rtd_plan_get_bdrf
+int rtd_version(void) { return 218; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt; 216: rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view, bit 3 of the evaluation flag word; 217: rtd_plan_request_surface, rtd_surface_samples, rtd_plan_get_bdrf; 218: rtd_plan_set_view_nt
 
 const char* rtd_last_error(void) { return g_err.c_str(); }
 
@@ -2558,12 +2612,21 @@ static bool view_band_consistent(const rtd_plan* p) {
   return true;
 }
 
+// mu = +-0.0 has no corrections of its own (the plane-parallel limit differs by hemisphere): refused in rtd_plan_set_view_nt's mode 1
+static const char* const VIEW_NT_ZERO = "mu = 0 is not accepted with the corrections at the angles (set_view_nt): the limit differs by hemisphere";
+static bool view_has_zero(const double* mu, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (mu[i] == 0.0) return true;
+  return false;
+}
+
 int rtd_plan_set_view_mu(rtd_plan* p, int32_t nmu, const double* mu, int32_t per_column) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
   if (nmu <= 0) {  // withdraw the request (the buffers, if any, stay with the plan)
     p->view_nmu = 0;
     p->view_mu_h.clear();
     p->view_stale = true;
+    p->view_u_resident = false;
     return 0;
   }
   if (!mu) return fail(RTD_ERR_ARG, "set_view_mu: null angles");
@@ -2571,6 +2634,7 @@ int rtd_plan_set_view_mu(rtd_plan* p, int32_t nmu, const double* mu, int32_t per
   const int64_t n = (per_column ? (int64_t)p->d.C : 1) * nmu;
   for (int64_t i = 0; i < n; ++i)
     if (!(std::fabs(mu[i]) <= 1.0)) return fail(RTD_ERR_ARG, "mu values must be between -1 and 1");
+  if (p->view_nt_mode == 1 && view_has_zero(mu, n)) return fail(RTD_ERR_ARG, VIEW_NT_ZERO);
   std::vector<double> keep(mu, mu + n);
   std::swap(keep, p->view_mu_h);
   const int old_nmu = p->view_nmu;
@@ -2584,17 +2648,25 @@ int rtd_plan_set_view_mu(rtd_plan* p, int32_t nmu, const double* mu, int32_t per
     return fail(RTD_ERR_ARG, "set_view_mu: the columns of a band profile must carry identical angles");
   }
   p->view_stale = true;
+  p->view_u_resident = false;  // (the next evaluation forms the view of u at the new angles; until then view_refused says so)
   return 0;
 }
 
-// the basis of the requested angles (when stale) and the interpolation of the resident results into ev_view_u / ev_view_u0, on the
-// plan's stream.  Every fetch drains the stream before it returns, so no copy reads view_mu_h when set_view_mu next replaces it.
-static int view_queued(rtd_plan* p, bool want_u, bool want_u0) {
+int rtd_plan_set_view_nt(rtd_plan* p, int32_t mode) {
+  if (!p) return fail(RTD_ERR_ARG, "null plan");
+  if (mode != 0 && mode != 1) return fail(RTD_ERR_ARG, "set_view_nt: the mode must be 0 (interpolated) or 1 (at the angles)");
+  if (mode == 1 && view_has_zero(p->view_mu_h.data(), (int64_t)p->view_mu_h.size())) return fail(RTD_ERR_ARG, VIEW_NT_ZERO);
+  if (mode != p->view_nt_mode) p->view_u_resident = false;
+  p->view_nt_mode = mode;
+  return 0;
+}
+
+// The basis of the requested angles when the device's copy is stale, on the plan's stream.  Every fetch drains the stream before it
+// returns, so no copy reads view_mu_h when set_view_mu next replaces it.
+static int view_basis_queued(rtd_plan* p) {
   HIP_TRY(hipSetDevice(p->device));
-  const ResultShape r(p);
-  const int64_t N = p->d.N, nmu = p->view_nmu, rows = p->view_per_column ? r.C : 1, n = rows * nmu;
+  const int64_t N = p->d.N, nmu = p->view_nmu, rows = p->view_per_column ? p->d.C : 1, n = rows * nmu;
   int rc;
-  int* flag = nullptr;
   (void)hipGetLastError();
   if (p->view_stale) {
     if ((rc = grow(p, p->view_mu, n)) || (rc = grow(p, p->view_b, N)) || (rc = grow(p, p->view_l, n * N)) ||
@@ -2604,25 +2676,40 @@ static int view_queued(rtd_plan* p, bool want_u, bool want_u0) {
     HIP_TRY(hipMemcpyAsync(p->view_mu, p->view_mu_h.data(), (size_t)n * 8, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipMemcpyAsync(p->view_b, b.data(), (size_t)N * 8, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));  // (b is a local; the basis is formed once per request, not per fetch)
-    flag = reinterpret_cast<int*>(p->view_flag.p);
+    int* flag = reinterpret_cast<int*>(p->view_flag.p);
     hipLaunchKernelGGL(rtd_view_basis_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p->stream, (const double*)p->view_mu, (long)n,
                        (const double*)p->d.mu, (const double*)p->view_b, (int)N, p->view_l.p, flag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_view_basis_kernel: ") + hipGetErrorString(e));
     p->view_stale = false;
   }
-  flag = reinterpret_cast<int*>(p->view_flag.p);
+  return 0;
+}
+
+// out [c0 .. c0 + cnt)[nmu][E] = the interpolant of X [cnt][2N][E], the results of those columns (X points at the first of them)
+static int view_apply_queued(rtd_plan* p, const double* X, int64_t E, int64_t c0, int64_t cnt, double* out) {
+  const int64_t N = p->d.N, nmu = p->view_nmu, total = cnt * nmu * E;
   const long ls = p->view_per_column ? (long)(nmu * N) : 0, fs = p->view_per_column ? (long)nmu : 0;
-  struct Pass { bool on; const double* X; int64_t E; DevBuf* out; } pass[2] = {{want_u, p->ev_u, r.nt * r.np, &p->ev_view_u},
+  const int* flag = reinterpret_cast<const int*>(p->view_flag.p);
+  hipLaunchKernelGGL(rtd_view_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, (const double*)p->view_l + c0 * ls, ls,
+                     flag + c0 * fs, fs, X, (int)N, (int)nmu, (long)E, (long)cnt, out + c0 * nmu * E);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_view_apply_kernel: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// the basis (when stale) and the interpolation of the resident results into ev_view_u / ev_view_u0, on the plan's stream.  The view of u
+// that an evaluation formed itself (rtd_plan_set_view_nt, mode 1: view_refused has seen that it is resident) is left as it is.
+static int view_queued(rtd_plan* p, bool want_u, bool want_u0) {
+  int rc = view_basis_queued(p);
+  if (rc) return rc;
+  const ResultShape r(p);
+  struct Pass { bool on; const double* X; int64_t E; DevBuf* out; } pass[2] = {{want_u && !p->view_u_resident, p->ev_u, r.nt * r.np, &p->ev_view_u},
                                                                               {want_u0, p->ev_u0, r.nt, &p->ev_view_u0}};
   for (const Pass& q : pass) {
     if (!q.on) continue;
-    const int64_t total = r.C * nmu * q.E;
-    if ((rc = grow(p, *q.out, total))) return rc;
-    hipLaunchKernelGGL(rtd_view_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, (const double*)p->view_l, ls,
-                       (const int*)flag, fs, q.X, (int)N, (int)nmu, (long)q.E, (long)r.C, q.out->p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_view_apply_kernel: ") + hipGetErrorString(e));
+    if ((rc = grow(p, *q.out, r.C * p->view_nmu * q.E))) return rc;
+    if ((rc = view_apply_queued(p, q.X, q.E, 0, r.C, q.out->p))) return rc;
   }
   return 0;
 }
@@ -2632,6 +2719,9 @@ static int view_refused(rtd_plan* p, const double* u_mu) {
   if (p->view_nmu <= 0) return fail(RTD_ERR_STATE, "set_view_mu must precede fetch_view");
   if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
   if (u_mu && !p->res_has_u) return fail(RTD_ERR_STATE, "fetch_view: the latest evaluation formed no u (no azimuths, or u was not wanted)");
+  if (u_mu && p->view_nt_mode == 1 && p->res_nt && !p->view_u_resident)
+    return fail(RTD_ERR_STATE, "fetch_view: with the corrections at the angles (set_view_nt) the view of u is formed by the evaluation, and the "
+                               "angles or the mode were set after the latest one: evaluate again");
   return 0;
 }
 

@@ -105,6 +105,15 @@ struct RtdNt {
   double* R;               // [C][2][2][NP][L]  other-layer sums: [antiderivative][up|down]
 };
 
+// the corrections at the viewing angles themselves (rtd_nt_view.hip): the angles, the other-layer sums and the view buffer of one window
+struct RtdNtView {
+  int nmu;
+  long mu_stride;    // doubles from one column's angles to the next: nmu, or 0 for a list the columns share
+  const double* mu;  // [C][nmu] or [nmu]
+  double* T;         // [C][L][nmu]  other-layer sums of the angle's hemisphere, in the tau-order of the evaluation
+  double* out;       // [C][nmu][ntau][nphi]  the window's slice of the view of u
+};
+
 // raw (unprepared) per-column inputs on the device, for rtd_prep.hip
 struct RtdRaw {
   int nleg_all;        // phase-function moments given per layer (>= P)
@@ -129,6 +138,8 @@ bool rtd_bc_fuses_eval(const RtdDev& d);  // the boundary-condition kernel chose
 void rtd_launch_eval(const RtdDev& d, const RtdEval& e, hipStream_t s);
 void rtd_launch_nt_tables(const RtdDev& d, const RtdNt& nt, hipStream_t s);
 void rtd_launch_nt_apply(const RtdDev& d, const RtdNt& nt, const RtdEval& e, hipStream_t s);
+void rtd_launch_nt_view_tables(const RtdDev& d, const RtdNtView& v, int antider, hipStream_t s);
+void rtd_launch_nt_view_apply(const RtdDev& d, const RtdNt& nt, const RtdEval& e, const RtdNtView& v, hipStream_t s);
 void rtd_launch_bdrf_modes(const RtdDev& d, int nphi, const double* rho_qq, const double* rho_q0, hipStream_t s);
 void rtd_launch_surface_ocean(const RtdDev& d, int nphi, const double* par, long par_rows, int group, const double* mu0_raw,
                               hipStream_t s);  // rtd_surface_ocean.hip: bdrfq / bdrfq0 of RTD_SURFACE_OCEAN on the clustered azimuth grid

@@ -22,6 +22,18 @@ def view_angles(mu, rows, axis="C"):
     return mu
 
 
+def view_corrections(corrections, mu=None):
+    """The `corrections` keyword of ``Plan.set_view`` and of everything that passes it on -> the mode of rtd_plan_set_view_nt:
+    "interpolated" 0, "at_angles" 1.  With mu (already through ``view_angles``) the one refusal of "at_angles" is made here, before
+    the plan is touched: mu = 0 has no corrections of its own."""
+    if corrections not in ("interpolated", "at_angles"):
+        raise ValueError(f'corrections must be "interpolated" or "at_angles", not {corrections!r}.')
+    mode = int(corrections == "at_angles")
+    if mode and mu is not None and np.any(mu == 0):
+        raise ValueError('mu = 0 is not accepted with corrections="at_angles": the limit differs by hemisphere.')
+    return mode
+
+
 _RESULT = ("u", "u0", "flux_up", "flux_down_diffuse", "flux_down_direct")  # the C ABI's order of the result pointers
 _THERMAL = ("TEMPER", "WVNMLO", "WVNMHI", "BTEMP", "TTEMP", "TEMIS", "emissivity")  # the fields of rtd_thermal, in their order
 
@@ -92,6 +104,7 @@ class Plan:
         self._ev_shape = None      # (ntau, nphi) of the stored points: set_eval_points, evaluate_band
         self._band = None          # (P, K): set_band_weights
         self._view = None          # nmu: set_view
+        self._view_nt = 0          # set_view(corrections=): the mode of rtd_plan_set_view_nt the plan is in
         self._surface = None       # (model id, nphi, rows): request_surface
         self._sharded = False      # set_mode_shard
         self._nranks = None        # comm_init
@@ -358,23 +371,38 @@ class Plan:
 
     _VIEW = ("u_mu", "u0_mu")
 
-    def set_view(self, mu):
+    def set_view(self, mu, *, corrections="interpolated"):
         """Polar-angle cosines at which ``fetch_view`` / ``fetch_band_view`` (and "view" in the `want` of ``evaluate`` /
         ``evaluate_band``) return the radiances: mu [nmu] shared by the columns, or [C, nmu]; None withdraws the request
         (include/rtd.h: rtd_plan_set_view_mu).  mu > 0 is interpolated among the upward rows of u, every other mu -- 0 included --
         among the downward rows, as the reference's ``subroutines.interpolate`` does.  Sticky across solves and evaluations.
-        Under band weights, angles given per column must be the same for the columns of a profile."""
+        Under band weights, angles given per column must be the same for the columns of a profile.
+        corrections (keyword-only; include/rtd.h: rtd_plan_set_view_nt): "interpolated" (default) -- the Nakajima-Tanaka corrected u
+        of the nodes is interpolated; "at_angles" -- the uncorrected u is interpolated and TMS + IMS are evaluated at the angles
+        themselves, which is what resolves the solar aureole and glint geometry.  Then mu = 0 is a ValueError, and the view of u is
+        formed by the NEXT evaluation: ``fetch_view`` for u_mu before it is an error.  Ignored by a plan without corrections."""
+        if mu is not None:
+            mu = view_angles(mu, self.C)
+        mode = view_corrections(corrections, mu)
+        if mode == 0:
+            self._set_view_nt(0)  # (before the angles: a zero among them is refused while the plan is in the other mode)
         if mu is None:
             _lib.check(self._lib.rtd_plan_set_view_mu(self._h, 0, None, 0))
             self._view = None
             return
-        mu = view_angles(mu, self.C)
         if mu.ndim == 2 and self._band is not None:
             per_profile = mu.reshape(self._band[0], self.C // self._band[0], -1)
             if not np.array_equal(per_profile, np.broadcast_to(per_profile[:, :1], per_profile.shape)):
                 raise ValueError("mu must be the same for the columns of a band profile.")
         _lib.check(self._lib.rtd_plan_set_view_mu(self._h, mu.shape[-1], _lib.dptr(mu), int(mu.ndim == 2)))
         self._view = mu.shape[-1]
+        self._set_view_nt(mode)
+
+    def _set_view_nt(self, mode):
+        """The plan's mode of rtd_plan_set_view_nt, changed only when it differs: a plan that never asks makes no call for it."""
+        if mode != self._view_nt:
+            _lib.check(self._lib.rtd_plan_set_view_nt(self._h, mode))
+            self._view_nt = mode
 
     def _resident_shape(self):
         """(ntau, nphi) of the results the plan holds now, as the plan itself reports them (``_resident_ntau``; u_bytes =

@@ -76,6 +76,7 @@ SIGNATURES = {
     "rtd_plan_fetch_actinic": (C.c_int, [_vp] + [_dp] * 3),
     "rtd_plan_fetch_band_actinic": (C.c_int, [_vp] + [_dp] * 3),
     "rtd_plan_set_view_mu": (C.c_int, [_vp, C.c_int32, _dp, C.c_int32]),
+    "rtd_plan_set_view_nt": (C.c_int, [_vp, C.c_int32]),
     "rtd_plan_fetch_view": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_fetch_band_view": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_set_bdrf_samples":(C.c_int, [_vp, C.c_int32, _dp, _dp]),

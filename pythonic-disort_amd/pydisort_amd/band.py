@@ -8,7 +8,7 @@ Legendre moments of the P G columns (include/rtd.h: rtd_plan_set_columns_band) a
 weights (rtd_plan_set_band_weights).  Column p G + g throughout."""
 import numpy as np
 
-from ._engine import Plan, view_angles
+from ._engine import Plan, view_angles, view_corrections as _view_corrections
 from ._prepare import double_gauss
 from .batch import BatchSolution, _check_numeric_errors, _default_window, _nt_checks, _retention, _stream_counts, _thermal_inputs
 from ._surface import surface_request
@@ -207,14 +207,15 @@ class BandSolution:
         r = self._eval(levels, None, ("act",))
         return self._out(r["flux_act_up"] + r["flux_act_down_diffuse"] + r["flux_act_down_direct"])
 
-    def _set_view(self, mu):
+    def _set_view(self, mu, corrections="interpolated"):
         mu = view_angles(mu, self.P, "P")
-        self.plan.set_view(np.repeat(mu, self.G, axis=0) if mu.ndim == 2 else mu)
+        self.plan.set_view(np.repeat(mu, self.G, axis=0) if mu.ndim == 2 else mu, corrections=corrections)
 
-    def u_at(self, mu, levels, phi):
+    def u_at(self, mu, levels, phi, *, corrections="interpolated"):
         """Band radiance at the polar-angle cosines mu [nmu] or [P, nmu] -> [P, K, nmu, nlev, nphi]: every column's u is
-        interpolated in mu on the device (``BatchSolution.u_at``), then summed over the spectral points."""
-        self._set_view(mu)
+        interpolated in mu on the device (``BatchSolution.u_at``), then summed over the spectral points.  corrections="at_angles"
+        (keyword-only): the Nakajima-Tanaka corrections of every column are evaluated at mu itself before the sum."""
+        self._set_view(mu, corrections)
         return self._out(self._eval(levels, phi, ("view_u",))["u_mu"])
 
     def u0_at(self, mu, levels=None):
@@ -277,8 +278,8 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
 
 def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, levels=None, phi=None,
                         chunk_columns=0, NLeg=None, NFourier=None, delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None,
-                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False, mu=None, surface=None,
-                        NBDRF=None, NT_cor=False):
+                        bdrf_q0=None, thermal=None, device=0, numeric_errors="raise", *, actinic=False, mu=None,
+                        view_corrections="interpolated", surface=None, NBDRF=None, NT_cor=False):
     """Throughput form of ``pydisort_band`` (as ``solve_columns_streamed`` is of ``pydisort_batch``): ONE plan holds the inputs
     and the results of all P G columns, the intermediates of the solve live for `chunk_columns` columns at a time, the results at
     `levels` (None: all L + 1) and `phi` are reduced on the device and only the P band results travel to the host -- 1 / G of what
@@ -288,9 +289,12 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
     flux_act_up, flux_act_down_diffuse, flux_act_down_direct [P, K, nlev] (``Plan.fetch_band_actinic``).  NT_cor as in
     ``pydisort_band``: u is corrected per column on the device before it is reduced.  mu [nmu] or [P, nmu]: adds the band
     radiances at those polar-angle cosines, u_mu [P, K, nmu, nlev, nphi] (not with only_flux) and u0_mu [P, K, nmu, nlev]
-    (``BandSolution.u_at``, ``Plan.fetch_band_view``).  surface, NBDRF as in ``pydisort_band``."""
+    (``BandSolution.u_at``, ``Plan.fetch_band_view``); view_corrections="at_angles" evaluates the Nakajima-Tanaka corrections of u_mu
+    at mu itself (``Plan.set_view``; the angles are then set before the run, which forms the view).  surface, NBDRF as in
+    ``pydisort_band``."""
     if mu is not None:
         mu = view_angles(mu, np.shape(dtau_abs)[0] if np.ndim(dtau_abs) == 3 else 0, "P")
+    at_angles = bool(_view_corrections(view_corrections, mu)) and mu is not None
     if chunk_columns <= 0:
         chunk_columns = _default_window(only_flux, NFourier, NLeg, NQuad)
     _, sol = pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=NLeg, NFourier=NFourier,
@@ -301,12 +305,15 @@ def solve_band_streamed(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I
     try:
         phi = np.array([0.0]) if (only_flux or phi is None) else np.atleast_1d(np.asarray(phi, float))
         plan.set_eval_points(level_tau(plan.prep["tau"], levels), phi)
+        if at_angles:
+            sol._set_view(mu, view_corrections)
         plan.run()
         out = plan.fetch_band(want=("u0", "flux") if only_flux else ("u", "u0", "flux"))
         if actinic:
             out.update(plan.fetch_band_actinic())
         if mu is not None:
-            sol._set_view(mu)
+            if not at_angles:
+                sol._set_view(mu)
             out.update(plan.fetch_band_view(("u0",) if only_flux else ("u", "u0")))
     finally:
         plan.close()

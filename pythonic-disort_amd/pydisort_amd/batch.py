@@ -2,7 +2,7 @@
 reference solves one column per ``pydisort`` call)."""
 import numpy as np
 
-from ._engine import Plan, view_angles
+from ._engine import Plan, view_angles, view_corrections as _view_corrections
 from . import _nt
 from ._prepare import double_gauss, prepare_columns
 from ._surface import surface_request
@@ -142,12 +142,12 @@ class BatchSolution:
             raise ValueError("`is_derivative_wrt_tau` and `is_antiderivative_wrt_tau` cannot both be set.")
         return bool(is_derivative_wrt_tau)
 
-    def _eval(self, want, tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu=None):
+    def _eval(self, want, tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu=None, corrections="interpolated"):
         """One device evaluation of `want` for an evaluator: the order's check, then the view angles `mu` (``u_at`` / ``u0_at``), then
         the range check of tau -> the dict of ``Plan.evaluate``."""
         deriv = self._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         if mu is not None:
-            self.plan.set_view(mu)
+            self.plan.set_view(mu, corrections=corrections)
         return self.plan.evaluate(self._tau(tau), phi, is_antiderivative_wrt_tau, want=(want,), derivative=deriv)
 
     def u(self, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
@@ -178,12 +178,14 @@ class BatchSolution:
         r = self._eval("act", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)
         return r["flux_act_down_diffuse"], r["flux_act_down_direct"]
 
-    def u_at(self, mu, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+    def u_at(self, mu, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False, corrections="interpolated"):
         """u at the polar-angle cosines mu [nmu] or [C, nmu] -> [C, nmu, ntau, nphi]: the reference's ``subroutines.interpolate(u)``
         for the whole batch on the device -- barycentric polynomial interpolation in mu of the evaluated (Nakajima-Tanaka corrected)
         u, each hemisphere on its own; mu > 0 looks up, every other mu, 0 included, down (``Plan.set_view``).  Only u_mu leaves the
-        device."""
-        return self._eval("view_u", tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu)["u_mu"]
+        device.  corrections="at_angles" (keyword-only) interpolates the uncorrected u and evaluates the Nakajima-Tanaka corrections
+        at mu itself instead of interpolating them -- the choice near the sun's direction, where the full phase function's forward
+        peak is narrower than the node spacing; mu = 0 is then a ValueError.  Without NT_cor the two are the same."""
+        return self._eval("view_u", tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu, corrections)["u_mu"]
 
     def u0_at(self, mu, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
         """The azimuthal mean u0 at the polar-angle cosines mu [nmu] or [C, nmu] -> [C, nmu, ntau] (``u_at``)."""
@@ -351,7 +353,7 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
 
 
 def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=False, out=None, numeric_errors="raise",
-                           *, tau_order=0, actinic=False, mu=None):
+                           *, tau_order=0, actinic=False, mu=None, view_corrections="interpolated"):
     """Throughput form for large column counts: ONE plan holds the inputs and the results of all columns, the
     intermediates of the solve (~8 MB per cfg4 column) live for `chunk_columns` columns at a time (0: ~8 192 (column,
     mode) chains per window) and the device-to-host copies of a window overlap the kernels of the next (``Plan.run_fetch``).
@@ -377,6 +379,8 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
           [C, nmu, ntau], interpolated on the device in the same `tau_order` (``Plan.fetch_view``).  u may then be left out of `out`:
           it stays on the device and is neither copied nor returned.  A view array that is absent from `out` is allocated and ADDED
           to the caller's dict; one that is present is checked like the others and filled in place.
+    view_corrections : "interpolated" (default) or "at_angles", the `corrections` of ``Plan.set_view`` for u_mu: with NT_cor in cfg the
+          corrections are evaluated at mu itself, window by window, instead of being interpolated (mu = 0 is then a ValueError).
     Returns dict(u [C, NQuad, ntau, nphi] (absent when only_flux), u0, flux_up, flux_down_diffuse, flux_down_direct)."""
     if tau_order not in (-1, 0, 1):
         raise ValueError("tau_order must be -1, 0 or +1.")
@@ -384,6 +388,7 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
     C, ntau = tau.shape
     if mu is not None:
         mu = view_angles(mu, C)
+    at_angles = bool(_view_corrections(view_corrections, mu))
     if chunk_columns <= 0:
         chunk_columns = _default_window(only_flux, cfg.get("NFourier"), cfg.get("NLeg"), int(cfg["NQuad"]))
     _, sol = pydisort_batch(only_flux=only_flux, device=device, work_columns=chunk_columns, device_prepare=True,
@@ -402,7 +407,7 @@ def solve_columns_streamed(cfg, tau, phi, chunk_columns=0, device=0, only_flux=F
         act = {k: (C, ntau) for k in Plan._ACT} if actinic else {}
         view = {}
         if mu is not None:
-            plan.set_view(mu)
+            plan.set_view(mu, **(dict(corrections=view_corrections) if at_angles else {}))
             view["u0_mu"] = (C, mu.shape[-1], ntau)
             if not only_flux:
                 view["u_mu"] = (C, mu.shape[-1], ntau, len(phi))
