@@ -479,6 +479,55 @@ int rtd_plan_fetch_view(rtd_plan* plan, double* u_mu, double* u0_mu);
  * u0_mu): u_mu [P][K][nmu][ntau][nphi], u0_mu [P][K][nmu][ntau].  RTD_ERR_STATE without weights; a profile with a failed column
  * is NaN and the call returns RTD_ERR_NUMERIC, as rtd_plan_fetch_band. */
 int rtd_plan_fetch_band_view(rtd_plan* plan, double* u_mu, double* u0_mu);
+/* Lambertian albedo sweeps from one solve.  For a Lambertian surface of albedo A that emits (1 - A) E below the layers, every field
+ * x of the solution -- u, u0, flux_up, the diffuse flux_down, a view of u or u0, in any tau-order -- is, exactly in the
+ * discrete-ordinate system (the adding formula of 6S, MODTRAN and DISORT's albedo / transmissivity mode),
+ *   x(A) = x_black + kappa(A) x_below,   kappa(A) = (A F / pi + (1 - A) E) / (1 - A s)
+ * x_black: the caller's problem over a BLACK, non-emitting surface (the primary: nbdrf = 0, b_pos = 0; beam, b_neg, thermal sources,
+ * delta-M and Nakajima-Tanaka corrections as it likes -- the corrections do not see the surface); x_below: the same layers without
+ * any source, lit from below by unit isotropic intensity (the companion: b_pos = 1, nfourier 1, beam 0, nscoeffs 0, nbdrf 0);
+ * F = flux_down (diffuse + direct, VALUE order) of the primary at the bottom, s = flux_down of the companion at the bottom over pi,
+ * the spherical albedo.  kappa does not depend on tau: the formula holds for values, tau-antiderivatives and tau-derivatives alike.
+ * The direct flux does not change.  K albedos cost the two solves -- 1 + 1 / nfourier of one -- and an elementwise kernel.
+ * rtd_plan_couple_lambert couples the LATEST evaluations the two plans hold (run, run_fetch, evaluate, evaluate_band), on the device
+ * (rtd_lambert_kappa_kernel, rtd_lambert_couple_kernel; arithmetic and rounding bound csrc/rtd_lambert.h; one fma per output, no
+ * atomics: the bits depend on neither the launch geometry nor the window or chunk size):
+ *   albedo        [A] (albedo_rows = 1) or [C][A] (albedo_rows = C), every value in [0, 1]
+ *   fdown_bottom, sph_albedo [C]   F and s, caller-supplied (the caller evaluates both plans at the bottom once)
+ *   emission      [C] or NULL (= 0): E >= 0, the surface's black-body emission
+ *   u [C][A][NQuad][ntau][nphi], u0 [C][A][NQuad][ntau], flux_up, flux_down_diffuse [C][A][ntau]
+ *   u_mu [C][A][nmu][ntau][nphi], u0_mu [C][A][nmu][ntau]   with viewing angles set on BOTH plans (rtd_plan_set_view_mu): the
+ *                 primary's view of u as its evaluation or rtd_plan_fetch_view would return it (interpolated or at the angles), the
+ *                 companion's view of u0 beside it
+ * Any output pointer may be NULL; nothing is formed for it.  The coupled arrays are formed chunk of columns after chunk in a scratch
+ * block from the pool (RTD_LAMBERT_BYTES, default 256 MiB -- not a tuned number; one column at least) and copied out; nothing stays
+ * with either plan (the view outputs go through the plans' own view buffers, as rtd_plan_fetch_view does), and a plan that never asks
+ * allocates and launches nothing for this.  Synchronous.
+ * A column with 1 - A s <= 0 (or a non-finite factor) for one of its albedos is NaN in every output.
+ * RTD_ERR_ARG: a null plan, nalb < 1, an albedo outside [0, 1] or not finite, an emission negative or not finite, albedo_rows neither
+ * 1 nor C, a null albedo, fdown_bottom or sph_albedo.  RTD_ERR_STATE: the plans differ in ncols, nlayers, nquad or device; the
+ * companion's dims are not (nfourier 1, beam 0, nscoeffs 0, nbdrf 0); the primary has nbdrf != 0; either plan holds no evaluated
+ * results (as rtd_plan_fetch_actinic); the resident ntau or tau-order of the two differ; u is wanted but the primary's latest
+ * evaluation formed none; view outputs are wanted but angles are not set on both plans or nmu differs; a mode shard or a communicator
+ * is active.  RTD_ERR_NUMERIC as rtd_plan_fetch reports it, over both plans: the failed columns are NaN (u and u_mu: any mode of the
+ * primary; the others: mode 0 of either plan), the others keep their results. */
+int rtd_plan_couple_lambert(rtd_plan* primary, rtd_plan* companion, int32_t nalb, const double* albedo, int32_t albedo_rows,
+                            const double* fdown_bottom, const double* sph_albedo, const double* emission, double* u, double* u0,
+                            double* flux_up, double* flux_down_diffuse, double* u_mu, double* u0_mu);
+/* The same for a band: kappa differs per spectral point (F, s and possibly A depend on g), so the columns are coupled BEFORE the
+ * weighted sum over g, which rtd_band_reduce_kernel then forms with the primary's band weights, chunk of profiles after chunk.
+ * albedo_rows: 1, P (one list per profile) or C = P G (a spectral albedo).  u [P][K][A][NQuad][ntau][nphi], u0 [P][K][A][NQuad][ntau],
+ * the fluxes [P][K][A][ntau], the views [P][K][A][nmu][...].  RTD_ERR_STATE without weights on the primary.  A profile with a failed
+ * column in either plan is NaN, the others are kept, and the call returns RTD_ERR_NUMERIC.  Per-column angles must be identical
+ * within a profile (RTD_ERR_ARG, as rtd_plan_fetch_band_view). */
+int rtd_plan_couple_lambert_band(rtd_plan* primary, rtd_plan* companion, int32_t nalb, const double* albedo, int32_t albedo_rows,
+                                 const double* fdown_bottom, const double* sph_albedo, const double* emission, double* u, double* u0,
+                                 double* flux_up, double* flux_down_diffuse, double* u_mu, double* u0_mu);
+/* The plan-free form, like rtd_planck_band: kappa [ncols][A] by the kernel the plans use (the same bits), and flag [ncols] (may be
+ * NULL): 1 where 1 - A s <= 0 or a factor is not finite for one of the column's albedos.  albedo_rows 1 or ncols; host arrays in,
+ * host arrays out, synchronous; the argument errors of rtd_plan_couple_lambert. */
+int rtd_lambert_kappa(int32_t device, int64_t ncols, int32_t nalb, const double* albedo, int32_t albedo_rows,
+                      const double* fdown_bottom, const double* sph_albedo, const double* emission, double* kappa, int32_t* flag);
 /* device pointers of the result buffers of rtd_plan_run (for a device-side collective); any pointer may be NULL */
 int rtd_plan_result_dev_ptrs(rtd_plan* plan, void** u_dev, int64_t* u_bytes, void** flux_dev, int64_t* flux_bytes);
 
@@ -601,6 +650,8 @@ enum {
  *                         (default 0: large blocks go straight back to the runtime); the same as rtd_pool_set_limit
  *   RTD_SURFACE_BYTES     bytes of the scratch block in which the surface models' samples are formed, chunk of columns after chunk
  *                         (default 256 MiB; one column at least): rtd_plan_request_surface, rtd_surface_samples
+ *   RTD_LAMBERT_BYTES     bytes of the scratch block in which the coupled arrays of a Lambertian sweep are formed, chunk of columns
+ *                         after chunk (default 256 MiB; one column, or one band profile, at least): rtd_plan_couple_lambert, _band
  *   RTD_NO_PIPELINE       windows one after the other on one stream (no second hand-off slot, no eigen stream)
  *   RTD_BC_FORCE_PIVOT    fused boundary-condition kernels: =1 every elimination is redone by the column-pivoted LDS path (the
  *                         path of a failed speculation); =2 every chain of the 32-stream kernel takes the register-resident

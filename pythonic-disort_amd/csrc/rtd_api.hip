@@ -20,6 +20,7 @@
 #include "rtd_planck.h"
 #include "rtd_nt_prep.h"
 #include "rtd_surface.h"
+#include "rtd_lambert.h"
 #if !defined(__HIPCC__)
 // A host compiler sees this unit only over the stand-in runtime of tests/cpu, which RUNS the kernels of the unit it compiles, thread
 // by thread on heap memory, and replaces the other units by shadow launchers.  The ocean's mode kernel joins this unit there (one
@@ -27,6 +28,8 @@
 #include "rtd_surface_ocean.hip"
 // likewise the corrections at the viewing angles (one thread per (column, angle) / per output, no cross-lane step)
 #include "rtd_nt_view.hip"
+// and the Lambertian coupling (one thread per column / per output element)
+#include "rtd_lambert.hip"
 #endif
 
 namespace {
@@ -854,7 +857,7 @@ extern "C" {
 
 int rtd_comm_destroy(rtd_plan* p);
 
-int rtd_version(void) { return 218; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt; 216: rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view, bit 3 of the evaluation flag word; 217: rtd_plan_request_surface, rtd_surface_samples, rtd_plan_get_bdrf; 218: rtd_plan_set_view_nt
+int rtd_version(void) { return 219; }  // 210: rtd_plan_create_retained, rtd_plan_retained, rtd_comm_size; 211: rtd_pool_trim, rtd_pool_bytes (round 5); 212: rtd_pool_set_limit (large-block pool off by default), rtd_comm_transport (round 6); 213: rtd_band_mix, rtd_plan_set_columns_band, rtd_plan_set_band_weights, rtd_plan_fetch_band, rtd_plan_evaluate_band; 214: rtd_plan_fetch_actinic, rtd_plan_fetch_band_actinic; 215: rtd_plan_request_nt, rtd_plan_get_nt; 216: rtd_plan_set_view_mu, rtd_plan_fetch_view, rtd_plan_fetch_band_view, bit 3 of the evaluation flag word; 217: rtd_plan_request_surface, rtd_surface_samples, rtd_plan_get_bdrf; 218: rtd_plan_set_view_nt; 219: rtd_plan_couple_lambert, rtd_plan_couple_lambert_band, rtd_lambert_kappa
 
 const char* rtd_last_error(void) { return g_err.c_str(); }
 
@@ -2763,6 +2766,193 @@ int rtd_plan_fetch_band_view(rtd_plan* p, double* u_mu, double* u0_mu) {
   if (rc) return rc;
   if (!view_band_consistent(p)) return fail(RTD_ERR_ARG, "fetch_band_view: the columns of a band profile must carry identical angles");
   return drained(p, band_view_fetch_queued(p, u_mu, u0_mu));
+}
+
+// ---- Lambertian albedo sweeps (rtd_plan_couple_lambert, rtd_plan_couple_lambert_band; kernels rtd_lambert.hip) ------------------------
+// The scratch budget of the coupled arrays in doubles (RTD_LAMBERT_BYTES, default 256 MiB; not a tuned number).
+static int64_t lambert_budget() {
+  const char* env = getenv("RTD_LAMBERT_BYTES");
+  return std::max<long long>(env ? atoll(env) : (256ll << 20), 8) / 8;
+}
+
+// what the two entry points and the plan-free rtd_lambert_kappa refuse of the caller's arrays: rows_ok lists the admissible albedo_rows
+static int lambert_args_refused(int64_t C, int32_t nalb, const double* albedo, int64_t rows, const int64_t* rows_ok, int nrows_ok,
+                                const double* fdown, const double* sph, const double* emission) {
+  if (nalb < 1) return fail(RTD_ERR_ARG, "couple_lambert: nalb must be at least 1");
+  if (!albedo || !fdown || !sph) return fail(RTD_ERR_ARG, "couple_lambert: null albedo, fdown_bottom or sph_albedo");
+  bool ok = false;
+  for (int i = 0; i < nrows_ok; ++i) ok = ok || (rows >= 1 && rows == rows_ok[i]);
+  if (!ok) return fail(RTD_ERR_ARG, "couple_lambert: albedo_rows must be 1 or the number of columns (a band: or of profiles)");
+  for (int64_t i = 0; i < rows * nalb; ++i)
+    if (!(albedo[i] >= 0.0 && albedo[i] <= 1.0)) return fail(RTD_ERR_ARG, "couple_lambert: an albedo must lie in [0, 1] (row " + std::to_string(i / nalb) + ")");
+  if (emission)
+    for (int64_t c = 0; c < C; ++c)
+      if (!(emission[c] >= 0.0 && std::isfinite(emission[c])))
+        return fail(RTD_ERR_ARG, "couple_lambert: the emission must be finite and not negative (column " + std::to_string(c) + ")");
+  return 0;
+}
+
+static bool lambert_sharded(const rtd_plan* p) { return p->comm || p->d.m0 != 0 || p->d.mstep != 1 || p->d.mtot != p->d.M; }
+
+// the RTD_ERR_STATE cases of the two entry points
+static int lambert_state_refused(rtd_plan* a, rtd_plan* b, bool want_u, const double* u_mu, const double* u0_mu) {
+  if (a->d.C != b->d.C || a->d.L != b->d.L || a->d.N != b->d.N || a->device != b->device)
+    return fail(RTD_ERR_STATE, "couple_lambert: the two plans differ in columns, layers, streams or device");
+  if (b->d.M != 1 || b->d.beam || b->d.Ns != 0 || b->d.NBDRF != 0)
+    return fail(RTD_ERR_STATE, "couple_lambert: the companion must have one Fourier mode, no beam, no isotropic source and no BDRF");
+  if (a->d.NBDRF != 0) return fail(RTD_ERR_STATE, "couple_lambert: the primary must be solved over a black surface (nbdrf = 0)");
+  if (lambert_sharded(a) || lambert_sharded(b)) return fail(RTD_ERR_STATE, "couple_lambert is not combined with a mode shard or a communicator");
+  for (const rtd_plan* p : {a, b})
+    if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "couple_lambert: nothing to couple (a plan holds no evaluated results)");
+  if (a->ev_ntau != b->ev_ntau || a->res_order != b->res_order)
+    return fail(RTD_ERR_STATE, "couple_lambert: the two plans were evaluated at different numbers of points or in different tau-orders");
+  if (want_u && !a->res_has_u) return fail(RTD_ERR_STATE, "couple_lambert: the primary's latest evaluation formed no u (no azimuths, or u was not wanted)");
+  if (u_mu || u0_mu) {
+    if (a->view_nmu <= 0 || b->view_nmu <= 0) return fail(RTD_ERR_STATE, "couple_lambert: set_view_mu must precede the view outputs, on both plans");
+    if (a->view_nmu != b->view_nmu) return fail(RTD_ERR_STATE, "couple_lambert: the two plans hold different numbers of viewing angles");
+    int rc = view_refused(a, u_mu);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// Everything behind the refusals, on the primary's stream.  A block from the pool holds the caller's small arrays, kappa [C][A], the
+// column flags and the coupled arrays of one chunk of columns -- for a band of whole profiles, with their reduced arrays behind them;
+// output after output, chunk after chunk is coupled (reduced) there and copied out.  Nothing stays with either plan.
+static int lambert_queued(rtd_plan* a, rtd_plan* b, int32_t nalb, const double* albedo, int64_t rows, const double* fdown, const double* sph,
+                          const double* emission, double* u, double* u0, double* fup, double* fdn, double* u_mu, double* u0_mu, bool band) {
+  HIP_TRY(hipSetDevice(a->device));
+  int rc;
+  if (u_mu || u0_mu) {  // the views of the resident results, each on its own plan's stream
+    if ((rc = view_queued(a, u_mu != nullptr, u0_mu != nullptr)) || (rc = view_queued(b, false, true))) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));  // (the companion's evaluation and view must have landed before the primary's stream reads them)
+  b->stream_drained();
+  const ResultShape r(a);
+  const int64_t C = r.C, nt = r.nt, np = r.np, nmu = a->view_nmu;
+  const int64_t G = band ? a->band_G : 1, K = band ? a->band_K : 0, NA = nalb;
+  struct Item { double* host; const double *X, *Y; int64_t E; int nrep, mask, band_mask; } items[6];
+  int nitems = 0;
+  if (u) items[nitems++] = {u, a->ev_u, b->ev_u0, r.per_column_u(), (int)np, 7, 0xFFFF};
+  if (u0) items[nitems++] = {u0, a->ev_u0, b->ev_u0, r.per_column_u0(), 1, 3, 0xFF};
+  if (fup) items[nitems++] = {fup, a->ev_fl + r.flux_at(0), b->ev_fl + r.flux_at(0), nt, 1, 3, 0xFF};
+  if (fdn) items[nitems++] = {fdn, a->ev_fl + r.flux_at(1), b->ev_fl + r.flux_at(1), nt, 1, 3, 0xFF};
+  if (u_mu) items[nitems++] = {u_mu, a->ev_view_u, b->ev_view_u0, nmu * nt * np, (int)np, 7, 0xFFFF};
+  if (u0_mu) items[nitems++] = {u0_mu, a->ev_view_u0, b->ev_view_u0, nmu * nt, 1, 3, 0xFF};
+  // columns per chunk of an item: as many as fit the budget, one column (a band: one profile) at least
+  const int64_t budget = lambert_budget();
+  auto chunk_of = [&](const Item& it) { return G * std::min<int64_t>(C / G, std::max<int64_t>(1, budget / ((G + K) * NA * it.E))); };
+  int64_t work = 0;
+  for (int i = 0; i < nitems; ++i) work = std::max(work, chunk_of(items[i]) / G * (G + K) * NA * items[i].E);
+  const int64_t n_alb = rows * NA, n_small = n_alb + 3 * C + C * NA + (C + 1) / 2 + 1;
+  void* blk_v = nullptr;
+  size_t got = 0;
+  HIP_TRY(pooled_malloc(&blk_v, (size_t)(n_small + work) * 8, a->device, &got));
+  double* blk = static_cast<double*>(blk_v);
+  double *d_alb = blk, *d_f = d_alb + n_alb, *d_s = d_f + C, *d_e = d_s + C, *d_k = d_e + C, *d_work = blk + n_small;
+  int* d_flag = reinterpret_cast<int*>(d_k + C * NA);
+  hipStream_t st = a->stream;
+  (void)hipGetLastError();
+  hipError_t e = hipMemcpyAsync(d_alb, albedo, (size_t)n_alb * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_f, fdown, (size_t)C * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_s, sph, (size_t)C * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && emission) e = hipMemcpyAsync(d_e, emission, (size_t)C * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    rtd_launch_lambert_kappa(d_alb, (long)(C / rows), nalb, d_f, d_s, emission ? d_e : nullptr, a->d.col_status, b->d.col_status, (long)C, d_k,
+                             d_flag, st);
+    e = hipGetLastError();
+  }
+  for (int i = 0; i < nitems && e == hipSuccess; ++i) {
+    const Item& it = items[i];
+    const int64_t per = NA * it.E, chunk = chunk_of(it);
+    for (int64_t c0 = 0; c0 < C && e == hipSuccess; c0 += chunk) {
+      const int64_t cnt = std::min(chunk, C - c0);
+      rtd_launch_lambert_couple(it.X + c0 * it.E, it.Y + c0 * (it.E / it.nrep), d_k + c0 * NA, d_flag + c0, it.mask, (long)cnt, nalb, (long)it.E,
+                                it.nrep, d_work, st);
+      e = hipGetLastError();
+      if (e != hipSuccess) break;
+      if (!band) {
+        e = hipMemcpyAsync(it.host + c0 * per, d_work, (size_t)(cnt * per) * 8, hipMemcpyDeviceToHost, st);
+      } else {  // the chunk's profiles reduced over g behind the coupled arrays, with the primary's weights
+        const int64_t P = cnt / G;
+        double* red = d_work + cnt * per;
+        hipLaunchKernelGGL(rtd_band_reduce_kernel, dim3((unsigned)((P * per + 255) / 256)), dim3(256), 0, st, (const double*)d_work,
+                           (const double*)a->band_w, (const int*)a->d.col_status + c0, it.band_mask, (long)P, (int)G, (int)K, (long)per, red);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(it.host + (c0 / G) * K * per, red, (size_t)(P * K * per) * 8, hipMemcpyDeviceToHost, st);
+      }
+    }
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    pooled_free(blk, got, a->device);
+    return fail(RTD_ERR_HIP, std::string("couple_lambert: ") + hipGetErrorString(e));
+  }
+  rc = check_status(a, u != nullptr || u_mu != nullptr);  // (drains the primary's stream: the block is free behind it)
+  pooled_free(blk, got, a->device);
+  const std::string keep = g_err;
+  const int rc_b = check_status(b, false);
+  if (rc) g_err = keep;
+  return rc ? rc : rc_b;
+}
+
+static int lambert_entry(rtd_plan* a, rtd_plan* b, int32_t nalb, const double* albedo, int32_t rows, const double* fdown, const double* sph,
+                         const double* emission, double* u, double* u0, double* fup, double* fdn, double* u_mu, double* u0_mu, bool band) {
+  if (!a || !b) return fail(RTD_ERR_ARG, "null plan");
+  const int64_t C = a->d.C;
+  if (band && a->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede couple_lambert_band");
+  const int64_t rows_ok[3] = {1, C, band ? C / a->band_G : 1};
+  int rc = lambert_args_refused(C, nalb, albedo, rows, rows_ok, 3, fdown, sph, emission);
+  if (rc || (rc = lambert_state_refused(a, b, u != nullptr, u_mu, u0_mu))) return rc;
+  if (band && (u_mu || u0_mu) && !view_band_consistent(a))
+    return fail(RTD_ERR_ARG, "couple_lambert_band: the columns of a band profile must carry identical angles");
+  return drained(a, lambert_queued(a, b, nalb, albedo, rows, fdown, sph, emission, u, u0, fup, fdn, u_mu, u0_mu, band));
+}
+
+int rtd_plan_couple_lambert(rtd_plan* primary, rtd_plan* companion, int32_t nalb, const double* albedo, int32_t albedo_rows,
+                            const double* fdown_bottom, const double* sph_albedo, const double* emission, double* u, double* u0,
+                            double* flux_up, double* flux_down_diffuse, double* u_mu, double* u0_mu) {
+  return lambert_entry(primary, companion, nalb, albedo, albedo_rows, fdown_bottom, sph_albedo, emission, u, u0, flux_up, flux_down_diffuse,
+                       u_mu, u0_mu, false);
+}
+
+int rtd_plan_couple_lambert_band(rtd_plan* primary, rtd_plan* companion, int32_t nalb, const double* albedo, int32_t albedo_rows,
+                                 const double* fdown_bottom, const double* sph_albedo, const double* emission, double* u, double* u0,
+                                 double* flux_up, double* flux_down_diffuse, double* u_mu, double* u0_mu) {
+  return lambert_entry(primary, companion, nalb, albedo, albedo_rows, fdown_bottom, sph_albedo, emission, u, u0, flux_up, flux_down_diffuse,
+                       u_mu, u0_mu, true);
+}
+
+int rtd_lambert_kappa(int32_t device, int64_t ncols, int32_t nalb, const double* albedo, int32_t albedo_rows, const double* fdown_bottom,
+                      const double* sph_albedo, const double* emission, double* kappa, int32_t* flag) {
+  if (ncols < 1 || !kappa) return fail(RTD_ERR_ARG, "lambert_kappa: need ncols >= 1 and an output array");
+  const int64_t rows_ok[2] = {1, ncols};
+  int rc = lambert_args_refused(ncols, nalb, albedo, albedo_rows, rows_ok, 2, fdown_bottom, sph_albedo, emission);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  const int64_t C = ncols, NA = nalb, n_alb = (int64_t)albedo_rows * NA, total = n_alb + 3 * C + C * NA + (C + 1) / 2 + 1;
+  void* blk_v = nullptr;
+  size_t got = 0;
+  HIP_TRY(pooled_malloc(&blk_v, (size_t)total * 8, device, &got));
+  double* blk = static_cast<double*>(blk_v);
+  double *d_alb = blk, *d_f = d_alb + n_alb, *d_s = d_f + C, *d_e = d_s + C, *d_k = d_e + C;
+  int* d_flag = reinterpret_cast<int*>(d_k + C * NA);
+  hipError_t e = hipMemcpy(d_alb, albedo, (size_t)n_alb * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_f, fdown_bottom, (size_t)C * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_s, sph_albedo, (size_t)C * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess && emission) e = hipMemcpy(d_e, emission, (size_t)C * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    (void)hipGetLastError();
+    rtd_launch_lambert_kappa(d_alb, (long)(C / albedo_rows), nalb, d_f, d_s, emission ? d_e : nullptr, nullptr, nullptr, (long)C, d_k, d_flag,
+                             (hipStream_t)0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(kappa, d_k, (size_t)(C * NA) * 8, hipMemcpyDeviceToHost);  // (waits for the kernel)
+  else (void)hipStreamSynchronize((hipStream_t)0);
+  if (e == hipSuccess && flag) e = hipMemcpy(flag, d_flag, (size_t)C * 4, hipMemcpyDeviceToHost);
+  pooled_free(blk, got, device);
+  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("lambert_kappa: ") + hipGetErrorString(e));
+  return 0;
 }
 
 int rtd_plan_set_nt(rtd_plan* p, int32_t nleg_all, const double* weighted_leg_all, const double* f_arr,

@@ -143,5 +143,10 @@ void rtd_launch_nt_view_apply(const RtdDev& d, const RtdNt& nt, const RtdEval& e
 void rtd_launch_bdrf_modes(const RtdDev& d, int nphi, const double* rho_qq, const double* rho_q0, hipStream_t s);
 void rtd_launch_surface_ocean(const RtdDev& d, int nphi, const double* par, long par_rows, int group, const double* mu0_raw,
                               hipStream_t s);  // rtd_surface_ocean.hip: bdrfq / bdrfq0 of RTD_SURFACE_OCEAN on the clustered azimuth grid
+// rtd_lambert.hip: kappa [C][A] and the column flags; out [C][A][E] = X [C][E] + kappa Y [C][E / nrep], NaN where flag & mask
+void rtd_launch_lambert_kappa(const double* albedo, long group, int nalb, const double* fdown, const double* sph, const double* emission,
+                              const int* st_a, const int* st_b, long C, double* kappa, int* flag, hipStream_t s);
+void rtd_launch_lambert_couple(const double* X, const double* Y, const double* kappa, const int* flag, int mask, long C, int nalb, long E,
+                               int nrep, double* out, hipStream_t s);
 void rtd_launch_export(const RtdDev& d, int col, double* GC, double* K, double* B, double* Gim, double* G,
                        hipStream_t s);

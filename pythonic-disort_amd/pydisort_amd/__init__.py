@@ -5,10 +5,10 @@ returned callables; ``pydisort_batch`` solves many independent atmospheric colum
 numerics run in hand-written HIP kernels (librtd.so) reached through the C ABI of include/rtd.h.
 """
 from .pydisort import pydisort  # noqa: F401
-from .batch import pydisort_batch, BatchSolution, solve_columns_streamed  # noqa: F401
+from .batch import pydisort_batch, BatchSolution, LambertSweep, solve_columns_streamed  # noqa: F401
 from . import subroutines  # noqa: F401
-from .band import pydisort_band, BandSolution, solve_band_streamed  # noqa: F401
-from ._engine import Plan as _Plan, planck_band, band_mix  # noqa: F401
+from .band import pydisort_band, BandSolution, BandLambertSweep, solve_band_streamed  # noqa: F401
+from ._engine import Plan as _Plan, planck_band, band_mix, lambert_kappa  # noqa: F401
 from ._surface import surface_reflectance  # noqa: F401
 
 import contextlib as _contextlib
@@ -32,4 +32,4 @@ def pooled(nbytes=-1, device=0):
 
 
 __all__ = ["pydisort", "pydisort_batch", "BatchSolution", "solve_columns_streamed", "pydisort_band", "BandSolution",
-           "solve_band_streamed", "band_mix", "subroutines", "planck_band", "surface_reflectance", "pool_bytes", "pool_trim", "pool_set_limit", "pooled"]
+           "solve_band_streamed", "LambertSweep", "BandLambertSweep", "lambert_kappa", "band_mix", "subroutines", "planck_band", "surface_reflectance", "pool_bytes", "pool_trim", "pool_set_limit", "pooled"]

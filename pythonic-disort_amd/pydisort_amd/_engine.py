@@ -75,6 +75,29 @@ def _out_arrays(given, shapes):
     return out
 
 
+def lambert_arrays(albedo, rows_ok, fdown_bottom, sph_albedo, emission, Cn):
+    """The small arrays of a Lambertian sweep checked on the host, before the library sees them: albedo [A] or [rows, A] with rows in
+    `rows_ok` and every value in [0, 1]; fdown_bottom, sph_albedo [C]; emission a scalar or [C], finite and not negative, or None
+    -> (albedo, F, s, E) as C-contiguous float64 (E None: no emission)."""
+    alb = _f64(np.atleast_1d(np.asarray(albedo, dtype=np.float64)))
+    if alb.ndim not in (1, 2) or alb.shape[-1] < 1 or (alb.ndim == 2 and alb.shape[0] not in rows_ok):
+        raise ValueError(f"albedo must have the shape [A] or [rows, A] with rows in {sorted(set(rows_ok))} and A >= 1.")
+    if not np.all((alb >= 0) & (alb <= 1)):
+        raise ValueError("albedo values must be between 0 and 1.")
+    F, s = _f64(fdown_bottom), _f64(sph_albedo)
+    if F is None or s is None or F.shape != (Cn,) or s.shape != (Cn,):
+        raise ValueError(f"fdown_bottom and sph_albedo must have the shape [C = {Cn}].")
+    E = None
+    if emission is not None:
+        E = np.asarray(emission, dtype=np.float64)
+        if E.ndim > 1 or (E.ndim == 1 and E.shape != (Cn,)):
+            raise ValueError(f"emission must be a scalar or [C = {Cn}].")
+        E = _f64(np.broadcast_to(E, (Cn,)))
+        if not np.all((E >= 0) & np.isfinite(E)):
+            raise ValueError("emission must be finite and not negative.")
+    return alb, F, s, E
+
+
 def _thermal_struct(thermal, Cn, L, N):
     """The thermal dict of ``Plan.set_columns_thermal`` checked against the plan's (C, L, N) -> (rtd_thermal, the arrays it points
     into: they must outlive the call that takes the struct)."""
@@ -99,6 +122,7 @@ class Plan:
         2 lean (rtd_plan_create_retained_form)."""
         lib = _lib.load()
         self._lib = lib
+        self.device = int(device)
         # What later calls read, with its "nothing yet" value (the uploads below set some of it, so it comes first).
         self.solved = False        # solve / run / run_fetch / solve_bc; every upload and shard call clears it
         self._ev_shape = None      # (ntau, nphi) of the stored points: set_eval_points, evaluate_band
@@ -440,6 +464,51 @@ class Plan:
         arrays = self._view_arrays(self._band_shape("fetch_band_view"), want, None)
         self._checked_band(self._lib.rtd_plan_fetch_band_view(self._h, _lib.dptr(arrays["u_mu"]), _lib.dptr(arrays["u0_mu"])))
         return arrays
+
+    def evaluate_resident(self, tau, phi=None, antiderivative=False, derivative=False, keep_u=False):
+        """``evaluate`` into the plan's device buffers with nothing copied out: for ``couple_lambert`` behind it.  keep_u: u is formed
+        on the device (bit 3 of the flag word; needs azimuths).  A numerical failure is raised, or left to the call that reads the
+        buffers under numeric_errors == "nan"."""
+        tau, ntau, phi, nphi, flags, _ = self._eval_args(tau, phi, antiderivative, derivative, False, ())
+        self._checked_band(self._lib.rtd_plan_evaluate(self._h, ntau, _lib.dptr(tau), nphi, _lib.dptr(phi),
+                                                       flags | (8 if keep_u and nphi > 0 else 0), *[None] * 6))
+
+    def _couple_lambert(self, fn, lead, rows_ok, companion, albedo, fdown_bottom, sph_albedo, emission, want):
+        """What ``couple_lambert`` and ``couple_lambert_band`` share: the checks of the small arrays, the host arrays `lead` +
+        (A, ...) of what `want` names, the call."""
+        if not isinstance(companion, Plan) or (companion.C, companion.L, companion.N) != (self.C, self.L, self.N):
+            raise ValueError("couple_lambert: the companion must be a Plan of the same columns, layers and streams.")
+        alb, F, s, E = lambert_arrays(albedo, rows_ok, fdown_bottom, sph_albedo, emission, self.C)
+        ntau, nphi = self._resident_shape()
+        A = alb.shape[-1]
+        view = self._view_want(want)
+        nmu = self._after(self._view, "set_view", "couple_lambert with a view") if view else 0
+        shapes = {"u": (self.Q, ntau, nphi) if "u" in want and nphi > 0 else None, "u0": (self.Q, ntau) if "u0" in want else None,
+                  "flux_up": (ntau,) if "flux" in want else None, "flux_down_diffuse": (ntau,) if "flux" in want else None,
+                  "u_mu": (nmu, ntau, nphi) if "u" in view and nphi > 0 else None, "u0_mu": (nmu, ntau) if "u0" in view else None}
+        out = {k: None if shp is None else np.empty(lead + (A,) + shp) for k, shp in shapes.items()}
+        self._checked_band(fn(self._h, companion._h, A, _lib.dptr(alb), alb.shape[0] if alb.ndim == 2 else 1, _lib.dptr(F), _lib.dptr(s),
+                              _lib.dptr(E), *[_lib.dptr(out[k]) for k in shapes]))
+        return out
+
+    def couple_lambert(self, companion, albedo, fdown_bottom, sph_albedo, emission=None, want=("u", "u0", "flux")):
+        """Lambertian albedo sweep (include/rtd.h: rtd_plan_couple_lambert): this plan solved over a BLACK surface, `companion` the
+        same layers without a source lit from below by unit isotropic intensity (M = 1, no beam), both evaluated at the same points
+        in the same tau-order; the LATEST evaluations the two hold are coupled on the device, x_black + kappa(A) x_below.
+        albedo [A] or [C, A]; fdown_bottom, sph_albedo [C]: flux_down (diffuse + direct, value order) of this plan at the bottom and
+        flux_down of the companion there over pi; emission: scalar or [C] or None.  want: "u", "u0", "flux", and "view" / "view_u" /
+        "view_u0" with ``set_view`` on both plans -> dict(u [C, A, Q, ntau, nphi], u0 [C, A, Q, ntau], flux_up, flux_down_diffuse
+        [C, A, ntau], u_mu [C, A, nmu, ntau, nphi], u0_mu [C, A, nmu, ntau]); what `want` leaves out is None.  A failed column (of
+        either plan) is NaN (numeric_errors == "nan") or raises NumericalError."""
+        return self._couple_lambert(self._lib.rtd_plan_couple_lambert, (self.C,), (self.C,), companion, albedo, fdown_bottom, sph_albedo,
+                                    emission, want)
+
+    def couple_lambert_band(self, companion, albedo, fdown_bottom, sph_albedo, emission=None, want=("u", "u0", "flux")):
+        """``couple_lambert`` before the sum over the spectral points with every weight set of this plan (include/rtd.h:
+        rtd_plan_couple_lambert_band): albedo [A], [P, A] or [C = P G, A] (a spectral albedo) -> the same keys, [P, K, A, ...]."""
+        P, K = self._band_shape("couple_lambert_band")
+        return self._couple_lambert(self._lib.rtd_plan_couple_lambert_band, (P, K), (P, self.C), companion, albedo, fdown_bottom,
+                                    sph_albedo, emission, want)
 
     @staticmethod
     def _view_want(want):
@@ -832,6 +901,18 @@ def band_mix(dtau_abs, dtau_spec, omega_spec, Leg_spec, NLeg, delta_M=True, devi
     out = [np.empty((P * G, L)) for _ in range(3)] + [np.empty((P * G, L, NLeg))]
     _lib.check(_lib.load().rtd_band_mix(int(device), L, NLeg, C.byref(bs), *[_lib.dptr(v) for v in out]))
     return tuple(out)
+
+
+def lambert_kappa(albedo, fdown_bottom, sph_albedo, emission=None, device=0):
+    """The factor kappa(A) = (A F / pi + (1 - A) E) / (1 - A s) of a Lambertian albedo sweep as the device forms it, by the kernel
+    behind ``Plan.couple_lambert`` (include/rtd.h: rtd_lambert_kappa): albedo [A] or [C, A], fdown_bottom and sph_albedo [C],
+    emission scalar, [C] or None -> (kappa [C, A], flag [C]: 1 where 1 - A s <= 0 or a factor is not finite)."""
+    Cn = int(np.size(fdown_bottom))
+    alb, F, s, E = lambert_arrays(albedo, (Cn,), np.reshape(fdown_bottom, -1), np.reshape(sph_albedo, -1), emission, Cn)
+    kappa, flag = np.empty((Cn, alb.shape[-1])), np.zeros(Cn, dtype=np.int32)
+    _lib.check(_lib.load().rtd_lambert_kappa(int(device), Cn, alb.shape[-1], _lib.dptr(alb), Cn if alb.ndim == 2 else 1, _lib.dptr(F),
+                                             _lib.dptr(s), _lib.dptr(E), _lib.dptr(kappa), flag.ctypes.data_as(C.POINTER(C.c_int32))))
+    return kappa, flag
 
 
 def device_count():

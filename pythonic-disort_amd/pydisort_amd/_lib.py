@@ -79,6 +79,9 @@ SIGNATURES = {
     "rtd_plan_set_view_nt": (C.c_int, [_vp, C.c_int32]),
     "rtd_plan_fetch_view": (C.c_int, [_vp, _dp, _dp]),
     "rtd_plan_fetch_band_view": (C.c_int, [_vp, _dp, _dp]),
+    "rtd_plan_couple_lambert": (C.c_int, [_vp, _vp, C.c_int32, _dp, C.c_int32] + [_dp] * 9),
+    "rtd_plan_couple_lambert_band": (C.c_int, [_vp, _vp, C.c_int32, _dp, C.c_int32] + [_dp] * 9),
+    "rtd_lambert_kappa": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _dp, C.c_int32] + [_dp] * 4 + [C.POINTER(C.c_int32)]),
     "rtd_plan_set_bdrf_samples":(C.c_int, [_vp, C.c_int32, _dp, _dp]),
     "rtd_plan_request_surface": (C.c_int, [_vp, C.POINTER(rtd_surface)]),
     "rtd_surface_samples": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp, _dp, C.c_int32, _dp]),

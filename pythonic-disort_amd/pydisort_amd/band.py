@@ -8,9 +8,10 @@ Legendre moments of the P G columns (include/rtd.h: rtd_plan_set_columns_band) a
 weights (rtd_plan_set_band_weights).  Column p G + g throughout."""
 import numpy as np
 
-from ._engine import Plan, view_angles, view_corrections as _view_corrections
+from ._engine import Plan, lambert_kappa, view_angles, view_corrections as _view_corrections
 from ._prepare import double_gauss
-from .batch import BatchSolution, _check_numeric_errors, _default_window, _nt_checks, _retention, _stream_counts, _thermal_inputs
+from .batch import (BatchSolution, _check_numeric_errors, _default_window, _lambert_companion, _lambert_refusals, _nt_checks, _retention,
+                    _stream_counts, _thermal_inputs)
 from ._surface import surface_request
 
 
@@ -229,11 +230,93 @@ class BandSolution:
         r = self._eval(None, None, ("flux",))
         return self._out(net_flux_convergence(r["flux_up"], r["flux_down_diffuse"], r["flux_down_direct"]))
 
+    # ---- Lambertian albedo sweeps (pydisort_band(..., lambert_sweep=True)) ----
+    def lambert_terms(self):
+        """The UNREDUCED terms of the sweep -> dict(flux_down_bottom, spherical_albedo [P, G]) (``BatchSolution.lambert_terms``):
+        they differ per spectral point, which is why the coupling happens before the sum over g."""
+        return {k: v.reshape(self.P, self.G) for k, v in self.columns.lambert_terms().items()}
+
+    def lambert(self, albedo, emission=None, BTEMP=None):
+        """The band over the Lambertian albedos `albedo` [A], [P, A] or [P, G, A] (a spectral albedo), emitting (1 - A) x `emission`
+        (scalar, [P] or [P G]; or BTEMP likewise: the Planck function over the band of thermal=) -> ``BandLambertSweep``, whose
+        evaluators take levels and return [P, K, A, ...].  Every column is coupled on the device BEFORE the weighted sum over g
+        (``Plan.couple_lambert_band``)."""
+        self.columns._lambert_state("lambert")
+        per_col = [None if v is None or np.ndim(v) == 0 else _per_column(v, name, self.P, self.G) for v, name in ((emission, "emission"), (BTEMP, "BTEMP"))]
+        return BandLambertSweep(self, albedo, self.columns._lambert_emission(emission if per_col[0] is None else per_col[0],
+                                                                          BTEMP if per_col[1] is None else per_col[1]))
+
+
+class BandLambertSweep:
+    """Evaluators of a ``lambert_sweep=True`` band over a list of Lambertian albedos: what ``BandSolution`` returns with an albedo
+    axis after the K axis.  Each call evaluates the primary and the companion at the levels and couples every column on the device
+    before the spectral sum.
+
+    kappa : [P, G, A] the coupling factor of every column as the device formed it."""
+
+    def __init__(self, band, albedo, emission):
+        alb = np.asarray(albedo, float)
+        if alb.ndim == 3:
+            if alb.shape[:2] != (band.P, band.G):
+                raise ValueError(f"albedo must have the shape [A], [P = {band.P}, A] or [P, G = {band.G}, A].")
+            alb = alb.reshape(band.P * band.G, -1)
+        elif alb.ndim == 2 and alb.shape[0] != band.P:
+            raise ValueError(f"albedo must have the shape [A], [P = {band.P}, A] or [P, G = {band.G}, A].")
+        self.band, self.albedo, self.emission = band, alb, emission
+        t = band.columns._lambert
+        per_column = np.repeat(alb, band.G, axis=0) if (alb.ndim == 2 and alb.shape[0] == band.P and band.G > 1) else alb
+        kappa, self.kappa_flag = lambert_kappa(per_column, t["flux_down_bottom"], t["spherical_albedo"], emission, band.plan.device)
+        self.kappa = kappa.reshape(band.P, band.G, -1)
+
+    def _eval(self, levels, phi, want, mu=None, corrections="interpolated"):
+        band, a, b = self.band, self.band.plan, self.band.columns.lit_from_below.plan
+        if mu is not None:
+            band._set_view(mu, corrections)
+            mu = view_angles(mu, band.P, "P")
+            b.set_view(np.repeat(mu, band.G, axis=0) if mu.ndim == 2 else mu)
+        tau = level_tau(a.prep["tau"], levels)
+        direct = None
+        if want == "flux":
+            direct = a.evaluate_band(tau, None, want=("flux",))["flux_down_direct"]
+        else:
+            a.evaluate_resident(tau, phi, keep_u=want in ("u", "view_u"))
+        b.evaluate_resident(tau, None)
+        t = band.columns._lambert
+        out = a.couple_lambert_band(b, self.albedo, t["flux_down_bottom"], t["spherical_albedo"], self.emission, want=(want,))
+        out["flux_down_direct"] = direct
+        return {k: None if v is None else band._out(v) for k, v in out.items()}
+
+    def flux_up(self, levels=None):
+        """-> [P, K, A, nlev]"""
+        return self._eval(levels, None, "flux")["flux_up"]
+
+    def flux_down(self, levels=None):
+        """-> (diffuse [P, K, A, nlev], direct [P, K, A, nlev]: the primary's, broadcast)"""
+        r = self._eval(levels, None, "flux")
+        d = r["flux_down_diffuse"]
+        return d, np.ascontiguousarray(np.broadcast_to(np.expand_dims(r["flux_down_direct"], -2), d.shape))
+
+    def u0(self, levels=None):
+        """-> [P, K, A, NQuad, nlev]"""
+        return self._eval(levels, None, "u0")["u0"]
+
+    def u(self, levels, phi):
+        """-> [P, K, A, NQuad, nlev, nphi]"""
+        return self._eval(levels, phi, "u")["u"]
+
+    def u_at(self, mu, levels, phi, *, corrections="interpolated"):
+        """-> [P, K, A, nmu, nlev, nphi] (``BandSolution.u_at``)"""
+        return self._eval(levels, phi, "view_u", mu, corrections)["u_mu"]
+
+    def u0_at(self, mu, levels=None):
+        """-> [P, K, A, nmu, nlev]"""
+        return self._eval(levels, None, "view_u0", mu)["u0_mu"]
+
 
 def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg=None, NFourier=None,
                   delta_M=True, only_flux=False, b_pos=0, b_neg=0, bdrf_q=None, bdrf_q0=None, thermal=None, device=0,
                   work_columns=0, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False, surface=None,
-                  NBDRF=None, NT_cor=False):
+                  NBDRF=None, lambert_sweep=False, NT_cor=False):
     """P profiles x G spectral points of a band in one call.
 
     dtau_abs [P, G, L]: absorption optical thickness of each layer at each spectral point; dtau_spec, omega_spec [P, L, S]:
@@ -253,8 +336,13 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
     (``Plan.request_nt``): the mixture's full weighted phase function once per PROFILE ([P, L, NLeg_all] -- it does not depend on
     the spectral point), the IMS constants per column.  Needs delta_M, more moments in Leg_spec than NLeg, I0 > 0 in every column
     and mu0 away from the quadrature nodes (``ValueError``); not with ``thermal``; ignored with only_flux.
+    lambert_sweep=True: as in ``pydisort_batch`` -- the band is solved over a black, non-emitting surface with a lit-from-below
+    companion beside it (built through the same band mixture), and ``sol.lambert(albedo)`` returns the band over any list of
+    Lambertian albedos, also one that follows the spectral point; the same exclusions (``ValueError``).
     Everything else as in ``pydisort_batch``.  Not combined with mode shards or communicators.
     Returns (mu_arr, BandSolution)."""
+    if lambert_sweep:
+        _lambert_refusals(bdrf_q, bdrf_q0, None, surface, None, b_pos, thermal, _defer_solve)
     prep, w, squeeze = _band_inputs(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi0, weights, NLeg, NFourier, delta_M,
                                     only_flux, b_pos, b_neg, bdrf_q, bdrf_q0, thermal, surface, NBDRF)
     _check_numeric_errors(numeric_errors)
@@ -273,6 +361,13 @@ def pydisort_band(dtau_abs, dtau_spec, omega_spec, Leg_spec, NQuad, mu0, I0, phi
         plan.solve()
     G = w.shape[1]
     sol = BandSolution(plan, prep["C"] // G, G, squeeze)
+    if lambert_sweep:
+        if prep["thermal"] is not None:
+            sol.columns._thermal_band = (prep["thermal"]["WVNMLO"], prep["thermal"]["WVNMHI"])
+        Cn, N = prep["C"], prep["N"]
+        cols_c = dict(mu0=np.ones(Cn), I0=np.zeros(Cn), phi0=np.zeros(Cn), b_pos=np.ones((Cn, 1, N)), b_neg=None, bdrf_q=None, bdrf_q0=None)
+        prep_c = dict(prep, M=1, Ns=0, NBDRF=0, beam=False, cols=cols_c, thermal=None, surface=None, nt=0)
+        _lambert_companion(sol.columns, prep_c, device, work_columns, budget, form, plan.prep["tau"][:, -1:])
     return sol.mu_arr, sol
 
 

@@ -2,7 +2,7 @@
 reference solves one column per ``pydisort`` call)."""
 import numpy as np
 
-from ._engine import Plan, view_angles, view_corrections as _view_corrections
+from ._engine import Plan, lambert_kappa, planck_band, view_angles, view_corrections as _view_corrections
 from . import _nt
 from ._prepare import double_gauss, prepare_columns
 from ._surface import surface_request
@@ -192,11 +192,137 @@ class BatchSolution:
         return self._eval("view_u0", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu)["u0_mu"]
 
 
+    # ---- Lambertian albedo sweeps (pydisort_batch(..., lambert_sweep=True)) ----
+    lit_from_below = None  # the companion BatchSolution: the same layers without a source, lit from below by unit isotropic intensity;
+    #                        its u0_at(mu, 0) is the upward total transmittance
+    _lambert = None        # dict(flux_down_bottom [C], spherical_albedo [C]), held on the host for every coupling call
+    _thermal_band = None   # (WVNMLO, WVNMHI) of thermal=, for lambert(BTEMP=)
+
+    def _lambert_state(self, caller):
+        if self._lambert is None:
+            raise ValueError(f"{caller} needs a solution made with lambert_sweep=True.")
+        return self._lambert
+
+    def lambert_terms(self):
+        """The atmospheric-correction terms of the sweep -> dict(flux_down_bottom [C]: the downward flux, diffuse + direct, at the
+        bottom over a black surface; spherical_albedo [C]: flux_down of ``lit_from_below`` at the bottom over pi)."""
+        return dict(self._lambert_state("lambert_terms"))
+
+    def _lambert_emission(self, emission, BTEMP):
+        """emission / BTEMP of ``lambert`` -> [C] or None (``planck_band`` over the band of thermal=)."""
+        if BTEMP is None:
+            return emission
+        if emission is not None:
+            raise ValueError("Give either emission or BTEMP, not both.")
+        if self._thermal_band is None:
+            raise ValueError("BTEMP needs the band of thermal= (WVNMLO, WVNMHI).")
+        T = np.broadcast_to(np.asarray(BTEMP, float), (self.prep["C"],))
+        if T.ndim != 1 or not np.all(T >= 0):
+            raise ValueError("BTEMP must be a scalar or [C] and not negative.")
+        return planck_band(np.ascontiguousarray(T), *self._thermal_band, device=self.plan.device)
+
+    def lambert(self, albedo, emission=None, BTEMP=None):
+        """The same atmosphere over the Lambertian albedos `albedo` [A] or [C, A], emitting (1 - A) x `emission` (scalar or [C];
+        or BTEMP: the Planck function over the band of thermal=) -> ``LambertSweep``, whose evaluators carry an albedo axis after the
+        column axis.  Exact in the discrete-ordinate system: x(A) = x_black + kappa(A) x_below, coupled on the device
+        (``Plan.couple_lambert``); no solve is made."""
+        self._lambert_state("lambert")
+        return LambertSweep(self, albedo, self._lambert_emission(emission, BTEMP))
+
+
+class LambertSweep:
+    """Evaluators of a ``lambert_sweep=True`` solution over a list of Lambertian albedos: what ``BatchSolution`` returns with an
+    albedo axis after the column axis, and the same two tau-order keywords.  Each call evaluates the primary and ``lit_from_below``
+    at the points (an evaluation each, no solve on a retained plan) and couples them on the device.
+
+    kappa : [C, A] the coupling factor as the device formed it (csrc/rtd_lambert.h)."""
+
+    def __init__(self, sol, albedo, emission):
+        self.sol, self.albedo, self.emission = sol, np.asarray(albedo, float), emission
+        t = sol._lambert
+        self.kappa, self.kappa_flag = lambert_kappa(self._column_albedo(), t["flux_down_bottom"], t["spherical_albedo"], emission, sol.plan.device)
+
+    def _column_albedo(self):
+        """The albedo as the coupling calls take it: [A] or [C, A]."""
+        return self.albedo
+
+    def _couple(self, want):
+        t = self.sol._lambert
+        return self.sol.plan.couple_lambert(self.sol.lit_from_below.plan, self._column_albedo(), t["flux_down_bottom"], t["spherical_albedo"],
+                                            self.emission, want=want)
+
+    def _eval(self, want, tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu=None, corrections="interpolated"):
+        a, b = self.sol, self.sol.lit_from_below
+        deriv = a._order(is_antiderivative_wrt_tau, is_derivative_wrt_tau)
+        if mu is not None:
+            a.plan.set_view(mu, corrections=corrections)
+            b.plan.set_view(mu)
+        tau = a._tau(tau)
+        if want == "flux":  # (the one field the surface does not touch travels as the primary evaluates it)
+            self._direct = a.plan.evaluate(tau, None, is_antiderivative_wrt_tau, want=("flux",), derivative=deriv)["flux_down_direct"]
+        else:
+            a.plan.evaluate_resident(tau, phi, is_antiderivative_wrt_tau, deriv, keep_u=want in ("u", "view_u"))
+        b.plan.evaluate_resident(tau, None, is_antiderivative_wrt_tau, deriv)
+        return self._couple((want,))
+
+    def u(self, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """-> [C, A, NQuad, ntau, nphi]"""
+        return self._eval("u", tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["u"]
+
+    def u0(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """-> [C, A, NQuad, ntau]"""
+        return self._eval("u0", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["u0"]
+
+    def flux_up(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """-> [C, A, ntau]"""
+        return self._eval("flux", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["flux_up"]
+
+    def flux_down(self, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """-> (diffuse [C, A, ntau], direct [C, A, ntau]); the direct flux does not see the surface: the primary's, broadcast."""
+        diffuse = self._eval("flux", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau)["flux_down_diffuse"]
+        return diffuse, np.ascontiguousarray(np.broadcast_to(self._direct[:, None, :], diffuse.shape))
+
+    def u_at(self, mu, tau, phi, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False, corrections="interpolated"):
+        """-> [C, A, nmu, ntau, nphi] (``BatchSolution.u_at``: the primary's view of u, interpolated or with its corrections at the
+        angles, coupled with the companion's view of u0)."""
+        return self._eval("view_u", tau, phi, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu, corrections)["u_mu"]
+
+    def u0_at(self, mu, tau, is_antiderivative_wrt_tau=False, *, is_derivative_wrt_tau=False):
+        """-> [C, A, nmu, ntau]"""
+        return self._eval("view_u0", tau, None, is_antiderivative_wrt_tau, is_derivative_wrt_tau, mu)["u0_mu"]
+
+
+def _lambert_refusals(bdrf_q, bdrf_q0, bdrf_samples, surface, mode_shard, b_pos, thermal, defer_solve):
+    """What ``lambert_sweep=True`` excludes: the primary is solved over a black, non-emitting surface; the surface belongs to the sweep."""
+    for name, v in (("bdrf_q", bdrf_q), ("bdrf_q0", bdrf_q0), ("bdrf_samples", bdrf_samples), ("surface", surface), ("mode_shard", mode_shard)):
+        if v is not None:
+            raise ValueError(f"lambert_sweep cannot be combined with {name}: the primary is solved over a black surface.")
+    if np.any(np.asarray(b_pos, float) != 0):
+        raise ValueError("lambert_sweep needs b_pos = 0: the surface's emission is given to lambert(emission=...).")
+    if thermal is not None and (thermal.get("BTEMP") is not None or thermal.get("emissivity") is not None):
+        raise ValueError("lambert_sweep: BTEMP and emissivity belong to lambert(BTEMP=...), not to thermal=.")
+    if defer_solve:
+        raise ValueError("lambert_sweep is not available in the streamed forms.")
+
+
+def _lambert_companion(sol, prep_c, device, work_columns, budget, form, bottom):
+    """The companion plan of a sweep, solved, and the two host-held terms: both plans evaluated at each column's bottom, in value
+    order, fluxes only.  sol: the primary's solution, which receives ``lit_from_below`` and the terms."""
+    plan_c = Plan(prep_c, device=device, work_columns=work_columns, retain_bytes=budget, retain_form=form or 0)
+    plan_c.numeric_errors = sol.plan.numeric_errors
+    plan_c.solve()
+    sol.lit_from_below = BatchSolution(plan_c, plan_c.prep)
+    bottom = np.ascontiguousarray(bottom)
+    ra, rb = sol.plan.evaluate(bottom, want=("flux",)), plan_c.evaluate(bottom, want=("flux",))
+    sol._lambert = dict(flux_down_bottom=np.ascontiguousarray(ra["flux_down_diffuse"][:, 0] + ra["flux_down_direct"][:, 0]),
+                        spherical_albedo=np.ascontiguousarray((rb["flux_down_diffuse"][:, 0] + rb["flux_down_direct"][:, 0]) / np.pi))
+
+
 def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLeg=None, NFourier=None,
                    b_pos=0, b_neg=0, only_flux=False, f_arr=0, NT_cor=False, bdrf_q=None, bdrf_q0=None,
                    s_poly_coeffs=None, device=0, bdrf_samples=None, NBDRF=None, mode_shard=None, work_columns=0,
                    device_prepare=False, numeric_errors="raise", retain="auto", retain_bytes=None, _defer_solve=False,
-                   thermal=None, surface=None):
+                   thermal=None, surface=None, lambert_sweep=False):
     """Like ``pydisort`` with a leading column axis on every atmospheric input:
     tau_arr, omega_arr, f_arr [C, L]; Leg_coeffs_all [C, L, NLeg_all]; mu0, I0, phi0 [C];
     b_pos / b_neg: scalar, [C], [C, N] or [C, N, NFourier]; s_poly_coeffs [C, L, Ns];
@@ -244,7 +370,17 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
     retain_bytes: the budget in bytes.  None (default): DEFAULT_RETAIN_BYTES = 16 GiB, and never more than three tenths of the
     free device memory -- the library is a guest on the GPU; a caller that wants BASELINE's 10^5-column batch retained passes what
     it is willing to give (50 GB lean).
+    lambert_sweep=True: the problem is solved as stated over a BLACK, non-emitting surface, and beside it a companion -- the same
+    layers without any source, lit from below by unit isotropic intensity, one Fourier mode: 1 / NFourier of a solve -- so that
+    ``sol.lambert(albedo)`` returns the solution over any list of Lambertian albedos without another solve (the adding formula, exact
+    in the discrete-ordinate system; include/rtd.h: rtd_plan_couple_lambert).  Right after the two solves both are evaluated at each
+    column's bottom (fluxes only): ``sol.lambert_terms()`` holds the downward flux over the black surface and the spherical albedo,
+    ``sol.lit_from_below`` is the companion's ``BatchSolution``.  On a plan of several windows that is not retained that evaluation,
+    like every evaluator call, solves the windows again.  Excludes bdrf_q, bdrf_q0, bdrf_samples, surface, mode_shard, a non-zero
+    b_pos, and BTEMP or emissivity inside thermal= (the surface's emission belongs to ``lambert(emission=...)``): ``ValueError``.
     All columns share NQuad, NLeg, NFourier and the layer count.  Returns (mu_arr, BatchSolution)."""
+    if lambert_sweep:
+        _lambert_refusals(bdrf_q, bdrf_q0, bdrf_samples, surface, mode_shard, b_pos, thermal, _defer_solve)
     tau_arr = np.atleast_2d(np.asarray(tau_arr, float))
     C, L = tau_arr.shape
     omega_arr = np.broadcast_to(np.asarray(omega_arr, float), (C, L))
@@ -349,6 +485,16 @@ def pydisort_batch(tau_arr, omega_arr, NQuad, Leg_coeffs_all, mu0, I0, phi0, NLe
             raise ValueError("Some quadrature angles come too close to `mu0`. Perturb `NQuad` or `mu0` to rectify this error.")
         plan.set_nt(*_nt.nt_inputs(prep, omega_arr, f_arr, Leg, NLeg, mu0))
     sol = BatchSolution(plan, prep)
+    if lambert_sweep:
+        if th is not None:
+            sol._thermal_band = (th["WVNMLO"], th["WVNMHI"])
+        # the companion needs no corrections: the first NLeg moments, through the raw device-prepared entry
+        raw_c = dict(tau_arr=tau_arr, omega_arr=omega_arr, leg=np.ascontiguousarray(Leg[..., :NLeg]), f_arr=f_arr, mu0=np.ones(C),
+                     I0=np.zeros(C), phi0=np.zeros(C), b_pos=np.ones((C, 1, N)), b_neg=None, s_poly=None, bdrf_q=None, bdrf_q0=None)
+        mu_c, W_c = double_gauss(N)
+        prep_c = dict(C=C, L=L, N=N, P=NLeg, M=1, Ns=0, NBDRF=0, beam=False, mu=mu_c, W=W_c, tau=tau_arr, raw=raw_c, thermal=None, nt=0,
+                      surface=None)
+        _lambert_companion(sol, prep_c, device, work_columns, budget, form, tau_arr[:, -1:])
     return sol.mu_arr, sol
 
 
