@@ -470,6 +470,55 @@ struct ResultShape {
   int64_t fl() const { return 3 * flux(); }
 };
 
+// Predicates and extents that several entry points share.
+// a mode shard or a communicator: the plan holds partial sums over the Fourier modes, which bands and the Lambertian coupling refuse
+bool sharded(const rtd_plan* p) { return p->comm || p->d.m0 != 0 || p->d.mstep != 1 || p->d.mtot != p->d.M; }
+// the result buffers hold an evaluation of a solve at the stored points (need_order: and res_order says in which tau-order)
+bool has_results(const rtd_plan* p, bool need_order) { return p->ev_ntau >= 1 && p->solved && !(need_order && p->res_order == rtd_plan::RES_NONE); }
+// rows [P][K] of a reduced array: the profiles of a band x the weight sets
+int64_t band_rows(const rtd_plan* p) { return (int64_t)(p->d.C / p->band_G) * p->band_K; }
+// a scratch budget of the environment in doubles (env: what getenv gave for RTD_SURFACE_BYTES or RTD_LAMBERT_BYTES; default 256 MiB,
+// not a tuned number), and the columns (rows, profiles) it holds at a time: as many as fit, one at least, `limit` at most
+int64_t budget_doubles(const char* env) { return std::max<long long>(env ? atoll(env) : (256ll << 20), 8) / 8; }
+int64_t columns_per_chunk(int64_t budget, int64_t per_column, int64_t limit) { return std::min<int64_t>(limit, std::max<int64_t>(1, budget / per_column)); }
+// blocks of a one-dimensional launch over n elements
+dim3 grid_1d(int64_t n, int64_t block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
+
+// A scratch block from the pool for the length of one call: it goes back when the owner leaves scope, on every path.  Nothing may
+// still read it then: the call ends in a synchronising copy or wait, or in finish(), which drains the stream of a failed call.
+struct Scratch {
+  void* p = nullptr;
+  size_t got = 0;
+  int dev = 0;
+  Scratch() = default;
+  Scratch(Scratch&& o) : p(o.p), got(o.got), dev(o.dev) { o.p = nullptr; }  // (move-only: the copies are not declared)
+  ~Scratch() {
+    if (p) pooled_free(p, got, dev);
+  }
+  hipError_t get(int64_t doubles, int device) {
+    dev = device;
+    return pooled_malloc(&p, (size_t)doubles * 8, device, &got);
+  }
+  double* data() const { return static_cast<double*>(p); }
+};
+// the caller's arrays one after the other from dst on, by synchronous copies (the plan-free entry points); a null array is left out
+struct HostPart { const double* src; int64_t n; };
+hipError_t upload_parts(double* dst, std::initializer_list<HostPart> parts) {
+  hipError_t e = hipSuccess;
+  for (const HostPart& q : parts) {
+    if (e == hipSuccess && q.src) e = hipMemcpy(dst, q.src, (size_t)q.n * 8, hipMemcpyHostToDevice);
+    dst += q.n;
+  }
+  return e;
+}
+// the end of a call that worked in a scratch block: 0, or the message of its first failed runtime call, behind a drained stream
+int finish(hipError_t e, hipStream_t s, const char* label) {
+  if (e == hipSuccess) return 0;
+  (void)hipStreamSynchronize(s);
+  (void)hipGetLastError();
+  return fail(RTD_ERR_HIP, std::string(label) + ": " + hipGetErrorString(e));
+}
+
 // a failed creation or a one-call form gives its plan back: the message of what went wrong survives rtd_plan_destroy; returns rc
 int destroy_keeping_error(rtd_plan* p, int rc) {
   const std::string keep = g_err;
@@ -752,7 +801,7 @@ int launch_windows(rtd_plan* p, bool with_solve, const RtdEval* ev, bool with_nt
         int rc = grow(p, p->sel_buf, ((int64_t)p->Cw * nsel + 1) / 2 + 1);
         if (rc) return rc;
         int* sel = reinterpret_cast<int*>(p->sel_buf.p);
-        hipLaunchKernelGGL(rtd_chunk_select_kernel, dim3((cnt + 127) / 128), dim3(128), 0, s, d, ev->tau + c0 * ev->ntau, ev->ntau, gpw, nsel, sel);
+        hipLaunchKernelGGL(rtd_chunk_select_kernel, grid_1d(cnt, 128), dim3(128), 0, s, d, ev->tau + c0 * ev->ntau, ev->ntau, gpw, nsel, sel);
         dsel.chunk_sel = sel;
         dsel.nsel = nsel;
       }
@@ -1534,9 +1583,9 @@ __global__ void rtd_band_moments_kernel(RtdBandDev b) {
 
 void band_mix_launch(const RtdBandDev& b, hipStream_t s) {
   const long C = b.P * b.G, n_cl = C * b.L, n_leg = n_cl * b.nleg;
-  hipLaunchKernelGGL(rtd_band_layers_kernel, dim3((unsigned)((n_cl + 255) / 256)), dim3(256), 0, s, b);
-  hipLaunchKernelGGL(rtd_band_tau_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, b);
-  hipLaunchKernelGGL(rtd_band_moments_kernel, dim3((unsigned)((n_leg + 255) / 256)), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(rtd_band_layers_kernel, grid_1d(n_cl), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(rtd_band_tau_kernel, grid_1d(C), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(rtd_band_moments_kernel, grid_1d(n_leg), dim3(256), 0, s, b);
 }
 
 // The inputs of the Nakajima-Tanaka corrections from what rtd_plan_set_columns_raw / _thermal / _band stage (rtd_plan_request_nt; the
@@ -1584,7 +1633,7 @@ __global__ void rtd_nt_ims_kernel(RtdDev d, RtdNtPrep q) {
 
 void nt_prepare_launch(const RtdDev& d, const RtdNtPrep& q, hipStream_t s) {  // behind rtd_launch_prepare: reads d.mu0, d.I0
   const long n = q.rows * d.L * q.nleg_all;
-  const dim3 grid((unsigned)((n + 255) / 256));
+  const dim3 grid = grid_1d(n);
   if (q.S > 0) hipLaunchKernelGGL(rtd_nt_wfull_band_kernel, grid, dim3(256), 0, s, q, d.L);
   else hipLaunchKernelGGL(rtd_nt_wfull_kernel, grid, dim3(256), 0, s, q, d.L);
   hipLaunchKernelGGL(rtd_nt_ims_kernel, dim3((unsigned)(((long)d.C + 3) / 4)), dim3(256), 0, s, d, q);
@@ -1781,12 +1830,8 @@ __global__ void rtd_view_apply_kernel(const double* l, long lstride, const int* 
   out[idx] = acc;
 }
 
-// The scratch budget of the surface samples in doubles (RTD_SURFACE_BYTES, default 256 MiB), and how a plan's upload spends it: the
-// staged parameters first, then the samples of `chunk` columns at a time -- as many as fit, at least one.
-int64_t surface_budget() {
-  const char* env = getenv("RTD_SURFACE_BYTES");
-  return std::max<long long>(env ? atoll(env) : (256ll << 20), 8) / 8;
-}
+// How a plan's upload spends the scratch budget of the surface samples (RTD_SURFACE_BYTES): the staged parameters first, then the
+// samples of `chunk` columns at a time.
 struct SurfLayout {
   int64_t par = 0, per_col = 0, chunk = 0;
   int64_t total() const { return par + chunk * per_col; }
@@ -1797,7 +1842,7 @@ void surface_layout(const rtd_plan* p, SurfLayout* out) {
   l.par = (int64_t)p->surf_par.size();
   if (p->surf_model != RTD_SURFACE_LAMBERT && p->surf_model != RTD_SURFACE_OCEAN) {  // (the ocean's kernel holds no samples in memory)
     l.per_col = ((int64_t)d.N * d.N + (d.beam ? d.N : 0)) * p->surf_nphi;
-    l.chunk = std::min<int64_t>(d.C, std::max<int64_t>(1, surface_budget() / l.per_col));
+    l.chunk = columns_per_chunk(budget_doubles(getenv("RTD_SURFACE_BYTES")), l.per_col, d.C);
   }
   *out = l;
 }
@@ -1818,7 +1863,7 @@ hipError_t surface_tables(const rtd_plan* p, const double* mu0_raw, int group, d
   v.par = blk; v.mu = d.mu; v.mup = d.beam ? mu0_raw : nullptr;
   if (v.model == RTD_SURFACE_LAMBERT) {
     const int64_t n = C * N * (N + 1);
-    hipLaunchKernelGGL(rtd_surface_lambert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, v, d.beam ? 1 : 0);
+    hipLaunchKernelGGL(rtd_surface_lambert_kernel, grid_1d(n), dim3(256), 0, s, d, v, d.beam ? 1 : 0);
     return hipGetLastError();
   }
   if (v.model == RTD_SURFACE_OCEAN) {  // modes on the clustered grid, one pass per pair of cosines (csrc/rtd_surface_ocean.hip)
@@ -1829,7 +1874,7 @@ hipError_t surface_tables(const rtd_plan* p, const double* mu0_raw, int group, d
   for (int64_t c0 = 0; c0 < C && e == hipSuccess; c0 += lay.chunk) {
     const int64_t cnt = std::min<int64_t>(lay.chunk, C - c0), nqq = cnt * N * N * v.nphi;
     v.c0 = c0; v.cnt = cnt; v.nrows = cnt * (N * N + (d.beam ? N : 0));
-    hipLaunchKernelGGL(rtd_surface_samples_kernel, dim3((unsigned)((v.nrows * v.nphi + 255) / 256)), dim3(256), 0, s, v);
+    hipLaunchKernelGGL(rtd_surface_samples_kernel, grid_1d(v.nrows * v.nphi), dim3(256), 0, s, v);
     RtdDev w = d;
     w.C = (int)cnt; w.bdrfq += c0 * NB * NP * NP; w.bdrfq0 += c0 * NB * NP;
     rtd_launch_bdrf_modes(w, v.nphi, v.out, d.beam ? v.out + nqq : nullptr, s);
@@ -1884,30 +1929,24 @@ int rtd_surface_samples(int32_t device, int32_t model, int64_t n, const double* 
       return fail(RTD_ERR_ARG, "surface_samples: row " + std::to_string(r) + ": mu and mup must lie in (0, 1]");
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(device));
-  const int64_t chunk = std::min<int64_t>(n, std::max<int64_t>(1, surface_budget() / (nphi + 6)));  // rows per pass
-  void* buf_v = nullptr;
-  size_t got = 0;
-  HIP_TRY(pooled_malloc(&buf_v, (size_t)(chunk * (nphi + 6)) * 8, device, &got));
-  double* buf = (double*)buf_v;
+  const int64_t chunk = columns_per_chunk(budget_doubles(getenv("RTD_SURFACE_BYTES")), nphi + 6, n);  // rows per pass
+  Scratch blk;
+  HIP_TRY(blk.get(chunk * (nphi + 6), device));
+  double* buf = blk.data();
   hipError_t e = hipSuccess;
   for (int64_t r0 = 0; r0 < n && e == hipSuccess; r0 += chunk) {
     const int64_t cnt = std::min<int64_t>(chunk, n - r0);
     RtdSurfDev v{};
     v.model = model; v.nphi = nphi; v.N = 0; v.group = 1; v.nrows = cnt; v.cnt = cnt; v.par_rows = cnt;
     v.par = buf; v.mu = buf + 4 * cnt; v.mup = buf + 5 * cnt; v.out = buf + 6 * cnt;
-    e = hipMemcpy(buf, params + 4 * r0, (size_t)cnt * 32, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(buf + 4 * cnt, mu + r0, (size_t)cnt * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(buf + 5 * cnt, mup + r0, (size_t)cnt * 8, hipMemcpyHostToDevice);
+    e = upload_parts(buf, {{params + 4 * r0, 4 * cnt}, {mu + r0, cnt}, {mup + r0, cnt}});
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(rtd_surface_samples_kernel, dim3((unsigned)((cnt * nphi + 255) / 256)), dim3(256), 0, (hipStream_t)0, v);
+      hipLaunchKernelGGL(rtd_surface_samples_kernel, grid_1d(cnt * nphi), dim3(256), 0, (hipStream_t)0, v);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(rho + r0 * nphi, v.out, (size_t)(cnt * nphi) * 8, hipMemcpyDeviceToHost);  // (waits for the kernel)
-    else (void)hipStreamSynchronize((hipStream_t)0);
   }
-  pooled_free(buf, got, device);
-  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("surface_samples: ") + hipGetErrorString(e));
-  return 0;
+  return finish(e, (hipStream_t)0, "surface_samples");
 }
 
 int rtd_plan_get_bdrf(rtd_plan* p, double* q, double* q0) {
@@ -1918,19 +1957,15 @@ int rtd_plan_get_bdrf(rtd_plan* p, double* q, double* q0) {
   if (NB <= 0 || (!q && !q0)) return 0;
   HIP_TRY(hipSetDevice(p->device));
   std::vector<double> h((size_t)(C * NB * NP * (q ? NP : 1)));
-  hipStream_t s = p->stream;
-  if (q) {  // rows and columns padded from N to NP on the device
-    HIP_TRY(hipMemcpyAsync(h.data(), d.bdrfq, (size_t)(C * NB * NP * NP) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+  // pad_streams undone: tables [N][N] of q, rows [N] of q0, padded from N to NP on the device
+  const struct { double* host; const double* dev; int64_t rows, rows_dev; } tabs[2] = {{q, d.bdrfq, N, NP}, {q0, d.bdrfq0, 1, 1}};
+  for (const auto& t : tabs) {
+    if (!t.host) continue;
+    HIP_TRY(hipMemcpyAsync(h.data(), t.dev, (size_t)(C * NB * t.rows_dev * NP) * 8, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
     for (int64_t b = 0; b < C * NB; ++b)
-      for (int64_t i = 0; i < N; ++i)
-        for (int64_t j = 0; j < N; ++j) q[(b * N + i) * N + j] = h[(size_t)((b * NP + i) * NP + j)];
-  }
-  if (q0) {
-    HIP_TRY(hipMemcpyAsync(h.data(), d.bdrfq0, (size_t)(C * NB * NP) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int64_t b = 0; b < C * NB; ++b)
-      for (int64_t i = 0; i < N; ++i) q0[b * N + i] = h[(size_t)(b * NP + i)];
+      for (int64_t i = 0; i < t.rows; ++i)
+        for (int64_t j = 0; j < N; ++j) t.host[(b * t.rows + i) * N + j] = h[(size_t)((b * t.rows_dev + i) * NP + j)];
   }
   p->stream_drained();
   return 0;
@@ -1940,24 +1975,17 @@ int rtd_planck_band(int32_t device, int64_t n, const double* T, const double* wv
   if (n < 0 || (n > 0 && (!T || !wvnmlo || !wvnmhi || !out))) return fail(RTD_ERR_ARG, "planck_band: null argument or n < 0");
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(device));
-  void* buf_v = nullptr;
-  size_t got = 0;
-  HIP_TRY(pooled_malloc(&buf_v, (size_t)n * 4 * 8, device, &got));
-  double* buf = (double*)buf_v;
-  const size_t nb = (size_t)n * 8;
-  hipError_t e = hipMemcpy(buf, T, nb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(buf + n, wvnmlo, nb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(buf + 2 * n, wvnmhi, nb, hipMemcpyHostToDevice);
+  Scratch blk;
+  HIP_TRY(blk.get(4 * n, device));
+  double* buf = blk.data();
+  hipError_t e = upload_parts(buf, {{T, n}, {wvnmlo, n}, {wvnmhi, n}});
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(rtd_planck_band_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)0, (long)n, buf,
+    hipLaunchKernelGGL(rtd_planck_band_kernel, grid_1d(n), dim3(256), 0, (hipStream_t)0, (long)n, buf,
                        buf + n, buf + 2 * n, buf + 3 * n);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpy(out, buf + 3 * n, nb, hipMemcpyDeviceToHost);  // (waits for the kernel)
-  else (void)hipStreamSynchronize((hipStream_t)0);
-  pooled_free(buf, got, device);
-  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("planck_band: ") + hipGetErrorString(e));
-  return 0;
+  if (e == hipSuccess) e = hipMemcpy(out, buf + 3 * n, (size_t)n * 8, hipMemcpyDeviceToHost);  // (waits for the kernel)
+  return finish(e, (hipStream_t)0, "planck_band");
 }
 
 // rtd_plan_set_columns_raw (th == nullptr: exactly its copies and launches), rtd_plan_set_columns_thermal (s_poly == nullptr,
@@ -1975,8 +2003,7 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   if (band) {
     if (const char* bad = band_bad(band, d.P)) return fail(RTD_ERR_ARG, bad);
     if ((int64_t)band->nprofiles * band->ngpoints != d.C) return fail(RTD_ERR_ARG, "band: the plan must have ncols = nprofiles x ngpoints");
-    if (p->comm || d.m0 != 0 || d.mstep != 1 || d.mtot != d.M)
-      return fail(RTD_ERR_STATE, "band inputs are not combined with a mode shard or a communicator");
+    if (sharded(p)) return fail(RTD_ERR_STATE, "band inputs are not combined with a mode shard or a communicator");
     nleg_all = d.P;  // the staging block holds the moments the solver uses
   }
   if (nleg_all < d.P) return fail(RTD_ERR_ARG, "nleg_all must be >= nleg");
@@ -2022,21 +2049,18 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     p->have_nt = false;  // (a buffer may move: on again below, once the new inputs are in place)
     if (int rc = nt_buffers(p, nt_rows, nt_all)) return rc;
   }
-  // staging block from the process-wide pool (a raw hipMalloc / hipFree pair synchronises the whole device per call)
-  void* raw_v = nullptr;
-  size_t raw_got = 0;
-  HIP_TRY(pooled_malloc(&raw_v, (size_t)total * 8, p->device, &raw_got));
-  double* raw = (double*)raw_v;
-  // the surface's scratch block (parameters, then the samples of one chunk of columns) likewise; both go back together
+  // staging block from the process-wide pool (a raw hipMalloc / hipFree pair synchronises the whole device per call), and the
+  // surface's scratch block (parameters, then the samples of one chunk of columns) likewise; both go back together, the staging
+  // block first (owners leave in reverse order)
+  Scratch surf_blk, raw_blk;
+  HIP_TRY(raw_blk.get(total, p->device));
+  double* raw = raw_blk.data();
   SurfLayout sl;
-  if (surf) surface_layout(p, &sl);
-  void* surf_v = nullptr;
-  size_t surf_got = 0;
   if (surf) {
-    const hipError_t es = pooled_malloc(&surf_v, (size_t)sl.total() * 8, p->device, &surf_got);
+    surface_layout(p, &sl);
+    const hipError_t es = surf_blk.get(sl.total(), p->device);
     if (es != hipSuccess) {
       (void)hipGetLastError();
-      pooled_free(raw, raw_got, p->device);
       return fail(RTD_ERR_HIP, std::string("request_surface: scratch block of ") + std::to_string(sl.total() * 8) + " bytes: " + hipGetErrorString(es));
     }
   }
@@ -2094,7 +2118,7 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   }
   std::vector<double> qh, q0h;
   if (e == hipSuccess && surf) {  // BDRF tables from the surface model; the rows of a band's P profiles serve its G points each
-    e = surface_tables(p, r.mu0, band && p->surf_rows != C ? (int)bG : 1, (double*)surf_v, sl, s);
+    e = surface_tables(p, r.mu0, band && p->surf_rows != C ? (int)bG : 1, surf_blk.data(), sl, s);
   } else if (e == hipSuccess && NB > 0) {  // BDRF tables: padded from N to NP on the host (small)
     qh = pad_streams(bdrf_q, C * NB, true, N, NP);
     q0h = pad_streams(bdrf_q0, C * NB, false, N, NP);
@@ -2103,8 +2127,8 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
   }
   if (e == hipSuccess && th) {  // (behind the BDRF tables and the quadrature on the plan's stream: the Kirchhoff sum reads both)
     const int64_t nE = C * (L + 3);
-    hipLaunchKernelGGL(rtd_thermal_emission_kernel, dim3((unsigned)((nE + 255) / 256)), dim3(256), 0, s, d, t);
-    hipLaunchKernelGGL(rtd_thermal_sources_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, d, t);
+    hipLaunchKernelGGL(rtd_thermal_emission_kernel, grid_1d(nE), dim3(256), 0, s, d, t);
+    hipLaunchKernelGGL(rtd_thermal_sources_kernel, grid_1d(C, 64), dim3(64), 0, s, d, t);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
@@ -2128,12 +2152,9 @@ static int set_columns_raw_impl(rtd_plan* p, const double* tau_arr, const double
     if (e == hipSuccess && tau_out) e = hipMemcpyAsync(tau_out, r.tau, (size_t)n_cl * 8, hipMemcpyDeviceToHost, s);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  else (void)hipStreamSynchronize(s);  // nothing may still read the block when it goes back to the pool
-  pooled_free(raw, raw_got, p->device);
-  if (surf) pooled_free(surf_v, surf_got, p->device);
   if (e != hipSuccess) {
     if (band) p->h_tau.clear();
-    return fail(RTD_ERR_HIP, std::string("set_columns_raw: ") + hipGetErrorString(e));
+    return finish(e, s, "set_columns_raw");
   }
   if (!band) p->h_tau.assign(tau_arr, tau_arr + C * L);
   p->new_columns(band != nullptr);
@@ -2173,28 +2194,20 @@ int rtd_band_mix(int32_t device, int32_t nlayers, int32_t nleg, const rtd_band* 
   HIP_TRY(hipSetDevice(device));
   const BandExtents x = band_extents(band, nlayers, nleg);
   const int64_t n_cl = x.n_cl, n_leg = x.n_leg, n_abs = x.n_abs, n_spec = x.n_spec, n_lspec = x.n_lspec;
-  void* buf_v = nullptr;
-  size_t got = 0;
-  HIP_TRY(pooled_malloc(&buf_v, (size_t)(3 * n_cl + n_leg + n_abs + 2 * n_spec + n_lspec) * 8, device, &got));
-  double* buf = (double*)buf_v;
-  double* in = buf + 3 * n_cl + n_leg;
-  const RtdBandDev b = band_dev(band, nlayers, nleg, buf, in);
-  hipError_t e = hipMemcpy(in, band->dtau_abs, (size_t)n_abs * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(in + n_abs, band->dtau_spec, (size_t)n_spec * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(in + n_abs + n_spec, band->omega_spec, (size_t)n_spec * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(in + n_abs + 2 * n_spec, band->leg_spec, (size_t)n_lspec * 8, hipMemcpyHostToDevice);
+  Scratch blk;
+  HIP_TRY(blk.get(3 * n_cl + n_leg + n_abs + 2 * n_spec + n_lspec, device));
+  double* in = blk.data() + 3 * n_cl + n_leg;
+  const RtdBandDev b = band_dev(band, nlayers, nleg, blk.data(), in);
+  hipError_t e = upload_parts(in, {{band->dtau_abs, n_abs}, {band->dtau_spec, n_spec}, {band->omega_spec, n_spec}, {band->leg_spec, n_lspec}});
   if (e == hipSuccess) {
     band_mix_launch(b, (hipStream_t)0);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(tau_arr, b.tau, (size_t)n_cl * 8, hipMemcpyDeviceToHost);  // (waits for the kernels)
-  else (void)hipStreamSynchronize((hipStream_t)0);
   if (e == hipSuccess) e = hipMemcpy(omega_arr, b.omega, (size_t)n_cl * 8, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(f_arr, b.f, (size_t)n_cl * 8, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(leg_all, b.leg, (size_t)n_leg * 8, hipMemcpyDeviceToHost);
-  pooled_free(buf, got, device);
-  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("band_mix: ") + hipGetErrorString(e));
-  return 0;
+  return finish(e, (hipStream_t)0, "band_mix");
 }
 
 int rtd_plan_set_bdrf_samples(rtd_plan* p, int32_t nphi, const double* rho_qq, const double* rho_q0) {
@@ -2331,16 +2344,94 @@ int rtd_plan_set_eval_order(rtd_plan* p, int32_t order) {
   return 0;
 }
 
-static int fetch_queued(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir) {
-  HIP_TRY(hipSetDevice(p->device));
+// out[p][k][e] = sum_g w[k][g] X[p G + g][e] on the plan's stream (rtd_band_reduce_kernel), then the copy of `out` to the host
+static hipError_t band_reduce(rtd_plan* p, const double* X, int mask, int64_t E, double* out, double* host) {
+  const int64_t G = p->band_G, K = p->band_K, P = p->d.C / G;
+  hipLaunchKernelGGL(rtd_band_reduce_kernel, grid_1d(P * E), dim3(256), 0, p->stream, X, (const double*)p->band_w,
+                     (const int*)p->d.col_status, mask, (long)P, (int)G, (int)K, (long)E, out);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(host, out, (size_t)(P * K * E) * 8, hipMemcpyDeviceToHost, p->stream);
+  return e;
+}
+
+// One output of a fetch, and the list of them that a call asks for.  Every fetch is a builder of such a list and one of two sinks:
+// copy_out takes each array as it lies, reduce_out (under band weights) its sum over the spectral points [P][K][per].
+//   builder            product          dev                  per          mask    reduced (slice of)
+//   result_products    u                ev_u                 Q ntau nphi  0xFFFF  rb_u
+//                      u0               ev_u0                Q ntau       0xFF    rb_u0
+//                      flux f = 0,1,2   ev_fl + f C ntau     ntau         0xFF    rb_fl (f of 3)
+//   actinic_products   f = 0, 1, 2      ev_act + f C ntau    ntau         0xFF    rb_act (f of 3)
+//   view_products      u_mu             ev_view_u            nmu ntau nphi 0xFFFF rb_view_u
+//                      u0_mu            ev_view_u0           nmu ntau     0xFF    rb_view_u0
+// mask: the bits of col_status that spoil the output -- every Fourier mode for u, mode 0 alone for u0 and the fluxes.  The list lives
+// on the caller's stack (rtd_plan_evaluate of one column comes through here: no allocation).
+struct Product {
+  double* host;       // the caller's array
+  const double* dev;  // where it lies on the device, all columns
+  int64_t per;        // doubles per column
+  int mask;
+  DevBuf* reduced;    // the band form's buffer, `nslices` arrays [P][K][per] of which this product is number `slice`
+  int slice, nslices;
+};
+struct Products {
+  Product v[6];
+  int n = 0;
+  bool all_modes = false;  // u was asked for (also where it has no extent, without azimuths): a failure in the modes m > 0 is the call's
+  void add(double* host, const double* dev, int64_t per, int mask, DevBuf* reduced, int slice = 0, int nslices = 1) {
+    if (host && per > 0) v[n++] = {host, dev, per, mask, reduced, slice, nslices};
+  }
+};
+// mode0: the list of a Lambertian companion -- the same outputs, each at its counterpart of Fourier mode 0 (u0 for u)
+static void result_products(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir, Products* xs, bool mode0 = false) {
   const ResultShape r(p);
-  hipStream_t s = p->stream;
-  if (u && r.np > 0) HIP_TRY(hipMemcpyAsync(u, p->ev_u, (size_t)r.u() * 8, hipMemcpyDeviceToHost, s));
-  if (u0) HIP_TRY(hipMemcpyAsync(u0, p->ev_u0, (size_t)r.u0() * 8, hipMemcpyDeviceToHost, s));
+  xs->add(u, mode0 ? p->ev_u0 : p->ev_u, mode0 ? r.per_column_u0() : r.per_column_u(), 0xFFFF, &p->rb_u);
+  xs->add(u0, p->ev_u0, r.per_column_u0(), 0xFF, &p->rb_u0);
   double* fls[3] = {flux_up, fdn, fdir};
-  for (int f = 0; f < 3; ++f)
-    if (fls[f]) HIP_TRY(hipMemcpyAsync(fls[f], p->ev_fl + r.flux_at(f), (size_t)r.flux() * 8, hipMemcpyDeviceToHost, s));
-  return check_status(p, u != nullptr);  // (u0 and the fluxes come from Fourier mode 0 alone)
+  for (int f = 0; f < 3; ++f) xs->add(fls[f], p->ev_fl + r.flux_at(f), r.nt, 0xFF, &p->rb_fl, f, 3);
+  xs->all_modes = xs->all_modes || u != nullptr;
+}
+static void actinic_products(rtd_plan* p, double* up, double* dn, double* dir, Products* xs) {
+  const ResultShape r(p);
+  double* outs[3] = {up, dn, dir};
+  for (int f = 0; f < 3; ++f) xs->add(outs[f], p->ev_act + r.flux_at(f), r.nt, 0xFF, &p->rb_act, f, 3);
+}
+static void view_products(rtd_plan* p, double* u_mu, double* u0_mu, Products* xs, bool mode0 = false) {
+  const ResultShape r(p);
+  const int64_t nmu = p->view_nmu;
+  xs->add(u_mu, mode0 ? p->ev_view_u0 : p->ev_view_u, nmu * r.nt * (mode0 ? 1 : r.np), 0xFFFF, &p->rb_view_u);
+  xs->add(u0_mu, p->ev_view_u0, nmu * r.nt, 0xFF, &p->rb_view_u0);
+  xs->all_modes = xs->all_modes || u_mu != nullptr;
+}
+// the device-to-host copies of the list on the plan's stream, then the status check (which drains the stream)
+static int copy_out(rtd_plan* p, const Products& xs) {
+  for (int i = 0; i < xs.n; ++i)
+    HIP_TRY(hipMemcpyAsync(xs.v[i].host, xs.v[i].dev, (size_t)(p->d.C * xs.v[i].per) * 8, hipMemcpyDeviceToHost, p->stream));
+  return check_status(p, xs.all_modes);
+}
+// the list reduced over the spectral points: every reduced buffer is grown before the first launch; each product is reduced and
+// copied out behind it (band_reduce); then the status check
+static int reduce_out(rtd_plan* p, const Products& xs, const char* label) {
+  const int64_t PK = band_rows(p);
+  int rc;
+  for (int i = 0; i < xs.n; ++i)
+    if ((rc = grow(p, *xs.v[i].reduced, xs.v[i].nslices * PK * xs.v[i].per))) return rc;
+  (void)hipGetLastError();
+  for (int i = 0; i < xs.n; ++i) {
+    const Product& x = xs.v[i];
+    const hipError_t e = band_reduce(p, x.dev, x.mask, x.per, x.reduced->p + x.slice * PK * x.per, x.host);
+    if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string(label) + ": " + hipGetErrorString(e));
+  }
+  return check_status(p, xs.all_modes);
+}
+// band_label: the name of the band form in the message of a failed reduction; null: the plain form
+static int deliver(rtd_plan* p, const Products& xs, const char* band_label) { return band_label ? reduce_out(p, xs, band_label) : copy_out(p, xs); }
+
+// the results at the stored points, as they lie or (band_label) reduced over the spectral points
+static int fetch_queued(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir, const char* band_label = nullptr) {
+  HIP_TRY(hipSetDevice(p->device));
+  Products xs;
+  result_products(p, u, u0, flux_up, fdn, fdir, &xs);
+  return deliver(p, xs, band_label);
 }
 
 // Whatever goes wrong, no copy into the caller's (pageable) arrays is left in flight behind the return: the caller may free or
@@ -2356,7 +2447,7 @@ static int drained(rtd_plan* p, int rc) {
 
 int rtd_plan_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
-  if (p->ev_ntau < 1 || !p->solved) return fail(RTD_ERR_STATE, "nothing to fetch");
+  if (!has_results(p, false)) return fail(RTD_ERR_STATE, "nothing to fetch");
   return drained(p, fetch_queued(p, u, u0, flux_up, fdn, fdir));
 }
 
@@ -2367,16 +2458,10 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
   if (!p->have_quad || !p->have_cols || p->ev_ntau < 1) return fail(RTD_ERR_STATE, "inputs or evaluation points missing");
   HIP_TRY(hipSetDevice(p->device));
   const ResultShape r(p);
-  // the arrays the caller wants: where each goes, where it lies on the device, its doubles per column
-  struct Part { double* host; const double* dev; int64_t per; } parts[5];
-  int nparts = 0;
-  if (u && r.np > 0) parts[nparts++] = {u, p->ev_u, r.per_column_u()};
-  if (u0) parts[nparts++] = {u0, p->ev_u0, r.per_column_u0()};
-  double* fls[3] = {flux_up, fdn, fdir};
-  for (int f = 0; f < 3; ++f)
-    if (fls[f]) parts[nparts++] = {fls[f], p->ev_fl + r.flux_at(f), r.nt};
+  Products xs;  // the arrays the caller wants: where each goes, where it lies on the device, its doubles per column
+  result_products(p, u, u0, flux_up, fdn, fdir, &xs);
   int64_t per_column = 0;
-  for (int k = 0; k < nparts; ++k) per_column += parts[k].per;
+  for (int k = 0; k < xs.n; ++k) per_column += xs.v[k].per;
   const size_t slab = (size_t)p->Cw * (size_t)per_column * 8;
   int rc;
   if (!p->copy_stream && (rc = acquire_stream(p->device, &p->copy_stream))) return rc;
@@ -2396,8 +2481,8 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
     const int64_t c0 = (int64_t)w * p->Cw, cnt = std::min<int64_t>(p->Cw, r.C - c0);
     HIP_TRY(hipEventSynchronize(p->ev_copied[w & 1]));
     const char* src = p->stage[w & 1];
-    for (int k = 0; k < nparts; src += cnt * parts[k].per * 8, ++k)
-      std::memcpy(parts[k].host + c0 * parts[k].per, src, (size_t)(cnt * parts[k].per) * 8);
+    for (int k = 0; k < xs.n; src += cnt * xs.v[k].per * 8, ++k)
+      std::memcpy(xs.v[k].host + c0 * xs.v[k].per, src, (size_t)(cnt * xs.v[k].per) * 8);
     return 0;
   };
   RtdEval e = make_eval(p, p->eval_order, true);
@@ -2412,8 +2497,8 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
     HIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_win[k], 0));
     char* dst = p->stage[k];
     hipStream_t cs = p->copy_stream;
-    for (int i = 0; i < nparts; dst += cnt * parts[i].per * 8, ++i)
-      HIP_TRY(hipMemcpyAsync(dst, parts[i].dev + c0 * parts[i].per, (size_t)(cnt * parts[i].per) * 8, hipMemcpyDeviceToHost, cs));
+    for (int i = 0; i < xs.n; dst += cnt * xs.v[i].per * 8, ++i)
+      HIP_TRY(hipMemcpyAsync(dst, xs.v[i].dev + c0 * xs.v[i].per, (size_t)(cnt * xs.v[i].per) * 8, hipMemcpyDeviceToHost, cs));
     HIP_TRY(hipEventRecord(p->ev_copied[k], cs));
     return 0;
   });
@@ -2422,7 +2507,7 @@ int rtd_plan_run_fetch(rtd_plan* p, double* u, double* u0, double* flux_up, doub
     if ((rc = drain(w))) return rc;
   p->res_order = p->eval_order;
   p->res_has_u = e.u != nullptr;
-  return check_status(p, u != nullptr);
+  return check_status(p, xs.all_modes);
 }
 
 int rtd_plan_result_dev_ptrs(rtd_plan* p, void** u_dev, int64_t* u_bytes, void** flux_dev, int64_t* flux_bytes) {
@@ -2479,8 +2564,7 @@ int rtd_plan_set_band_weights(rtd_plan* p, int32_t G, int32_t K, const double* w
     return 0;
   }
   if (K < 1 || !w || p->d.C % G != 0) return fail(RTD_ERR_ARG, "band weights: need nsets >= 1, weights and ncols % ngpoints == 0");
-  if (p->comm || p->d.m0 != 0 || p->d.mstep != 1 || p->d.mtot != p->d.M)
-    return fail(RTD_ERR_STATE, "band weights are not combined with a mode shard or a communicator");
+  if (sharded(p)) return fail(RTD_ERR_STATE, "band weights are not combined with a mode shard or a communicator");
   HIP_TRY(hipSetDevice(p->device));
   int rc = grow(p, p->band_w, (int64_t)K * G);
   if (rc) return rc;
@@ -2491,41 +2575,11 @@ int rtd_plan_set_band_weights(rtd_plan* p, int32_t G, int32_t K, const double* w
   return 0;
 }
 
-// out[p][k][e] = sum_g w[k][g] X[p G + g][e] on the plan's stream (rtd_band_reduce_kernel), then the copy of `out` to the host
-static hipError_t band_reduce(rtd_plan* p, const double* X, int mask, int64_t E, double* out, double* host) {
-  const int64_t G = p->band_G, K = p->band_K, P = p->d.C / G;
-  hipLaunchKernelGGL(rtd_band_reduce_kernel, dim3((unsigned)((P * E + 255) / 256)), dim3(256), 0, p->stream, X, (const double*)p->band_w,
-                     (const int*)p->d.col_status, mask, (long)P, (int)G, (int)K, (long)E, out);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(host, out, (size_t)(P * K * E) * 8, hipMemcpyDeviceToHost, p->stream);
-  return e;
-}
-
-// reduce the result buffers over the spectral points on the plan's stream, copy the reduced arrays out, check the status
-static int band_fetch_queued(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir) {
-  HIP_TRY(hipSetDevice(p->device));
-  const ResultShape r(p);
-  const int64_t PK = (int64_t)(p->d.C / p->band_G) * p->band_K, nt = r.nt, np = r.np, Eu = r.per_column_u(), Eu0 = r.per_column_u0();
-  double* fls[3] = {flux_up, fdn, fdir};
-  int rc;
-  if (u && np > 0 && (rc = grow(p, p->rb_u, PK * Eu))) return rc;
-  if (u0 && (rc = grow(p, p->rb_u0, PK * Eu0))) return rc;
-  if ((flux_up || fdn || fdir) && (rc = grow(p, p->rb_fl, 3 * PK * nt))) return rc;
-  (void)hipGetLastError();
-  hipError_t e = hipSuccess;
-  if (u && np > 0) e = band_reduce(p, p->ev_u, 0xFFFF, Eu, p->rb_u, u);
-  if (e == hipSuccess && u0) e = band_reduce(p, p->ev_u0, 0xFF, Eu0, p->rb_u0, u0);  // (u0 and the fluxes come from Fourier mode 0 alone)
-  for (int f = 0; f < 3; ++f)
-    if (e == hipSuccess && fls[f]) e = band_reduce(p, p->ev_fl + r.flux_at(f), 0xFF, nt, p->rb_fl + f * PK * nt, fls[f]);
-  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("fetch_band: ") + hipGetErrorString(e));
-  return check_status(p, u != nullptr);
-}
-
 int rtd_plan_fetch_band(rtd_plan* p, double* u, double* u0, double* flux_up, double* fdn, double* fdir) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
   if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede fetch_band");
-  if (p->ev_ntau < 1 || !p->solved) return fail(RTD_ERR_STATE, "nothing to fetch");
-  return drained(p, band_fetch_queued(p, u, u0, flux_up, fdn, fdir));
+  if (!has_results(p, false)) return fail(RTD_ERR_STATE, "nothing to fetch");
+  return drained(p, fetch_queued(p, u, u0, flux_up, fdn, fdir, "fetch_band"));
 }
 
 int rtd_plan_evaluate_band(rtd_plan* p, int32_t ntau, const double* tau, int32_t nphi, const double* phi, int32_t flags, double* u,
@@ -2534,7 +2588,7 @@ int rtd_plan_evaluate_band(rtd_plan* p, int32_t ntau, const double* tau, int32_t
   if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede evaluate_band");
   int rc = evaluate_queued(p, ntau, tau, nphi, phi, flags, u != nullptr || (flags & 8) != 0);
   if (rc) return rc;
-  return drained(p, band_fetch_queued(p, u, u0, flux_up, fdn, fdir));
+  return drained(p, fetch_queued(p, u, u0, flux_up, fdn, fdir, "fetch_band"));
 }
 
 // rtd_actinic_kernel over all columns into ev_act, on the plan's stream: everything it reads is held for all columns
@@ -2544,48 +2598,33 @@ static int actinic_queued(rtd_plan* p) {
   int rc = grow(p, p->ev_act, 3 * CT);
   if (rc) return rc;
   (void)hipGetLastError();
-  hipLaunchKernelGGL(rtd_actinic_kernel, dim3((unsigned)((CT + 255) / 256)), dim3(256), 0, p->stream, p->d, (const double*)p->ev_tau,
+  hipLaunchKernelGGL(rtd_actinic_kernel, grid_1d(CT), dim3(256), 0, p->stream, p->d, (const double*)p->ev_tau,
                      (const double*)p->ev_u0, (int)p->ev_ntau, (int)p->res_order, p->ev_act);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_actinic_kernel: ") + hipGetErrorString(e));
   return 0;
 }
 
-static int actinic_fetch_queued(rtd_plan* p, double* up, double* dn, double* dir) {
+static int actinic_fetch_queued(rtd_plan* p, double* up, double* dn, double* dir, const char* band_label = nullptr) {
   int rc = actinic_queued(p);
   if (rc) return rc;
-  const int64_t CT = (int64_t)p->d.C * p->ev_ntau;
-  double* outs[3] = {up, dn, dir};
-  for (int f = 0; f < 3; ++f)
-    if (outs[f]) HIP_TRY(hipMemcpyAsync(outs[f], p->ev_act + f * CT, (size_t)CT * 8, hipMemcpyDeviceToHost, p->stream));
-  return check_status(p, false);  // (u0 comes from Fourier mode 0 alone)
-}
-
-static int band_actinic_fetch_queued(rtd_plan* p, double* up, double* dn, double* dir) {
-  int rc = actinic_queued(p);
-  if (rc) return rc;
-  const int64_t PK = (int64_t)(p->d.C / p->band_G) * p->band_K, nt = p->ev_ntau, CT = p->d.C * nt;
-  if ((rc = grow(p, p->rb_act, 3 * PK * nt))) return rc;
-  double* outs[3] = {up, dn, dir};
-  for (int f = 0; f < 3; ++f) {
-    if (!outs[f]) continue;
-    hipError_t e = band_reduce(p, p->ev_act + f * CT, 0xFF, nt, p->rb_act + f * PK * nt, outs[f]);
-    if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("fetch_band_actinic: ") + hipGetErrorString(e));
-  }
-  return check_status(p, false);
+  if (band_label && (rc = grow(p, p->rb_act, 3 * band_rows(p) * p->ev_ntau))) return rc;  // (also when no output is asked for, as ever)
+  Products xs;  // (all_modes stays false: u0 comes from Fourier mode 0 alone)
+  actinic_products(p, up, dn, dir, &xs);
+  return deliver(p, xs, band_label);
 }
 
 int rtd_plan_fetch_actinic(rtd_plan* p, double* act_up, double* act_down_diffuse, double* act_down_direct) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
-  if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
+  if (!has_results(p, true)) return fail(RTD_ERR_STATE, "nothing to fetch");
   return drained(p, actinic_fetch_queued(p, act_up, act_down_diffuse, act_down_direct));
 }
 
 int rtd_plan_fetch_band_actinic(rtd_plan* p, double* act_up, double* act_down_diffuse, double* act_down_direct) {
   if (!p) return fail(RTD_ERR_ARG, "null plan");
   if (p->band_G <= 0) return fail(RTD_ERR_STATE, "set_band_weights must precede fetch_band_actinic");
-  if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
-  return drained(p, band_actinic_fetch_queued(p, act_up, act_down_diffuse, act_down_direct));
+  if (!has_results(p, true)) return fail(RTD_ERR_STATE, "nothing to fetch");
+  return drained(p, actinic_fetch_queued(p, act_up, act_down_diffuse, act_down_direct, "fetch_band_actinic"));
 }
 
 // the barycentric weights b_j = 1 / prod_{k != j} (x_j - x_k) of the plan's positive nodes: long double, k ascending, scaled by
@@ -2680,7 +2719,7 @@ static int view_basis_queued(rtd_plan* p) {
     HIP_TRY(hipMemcpyAsync(p->view_b, b.data(), (size_t)N * 8, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));  // (b is a local; the basis is formed once per request, not per fetch)
     int* flag = reinterpret_cast<int*>(p->view_flag.p);
-    hipLaunchKernelGGL(rtd_view_basis_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p->stream, (const double*)p->view_mu, (long)n,
+    hipLaunchKernelGGL(rtd_view_basis_kernel, grid_1d(n), dim3(256), 0, p->stream, (const double*)p->view_mu, (long)n,
                        (const double*)p->d.mu, (const double*)p->view_b, (int)N, p->view_l.p, flag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_view_basis_kernel: ") + hipGetErrorString(e));
@@ -2694,7 +2733,7 @@ static int view_apply_queued(rtd_plan* p, const double* X, int64_t E, int64_t c0
   const int64_t N = p->d.N, nmu = p->view_nmu, total = cnt * nmu * E;
   const long ls = p->view_per_column ? (long)(nmu * N) : 0, fs = p->view_per_column ? (long)nmu : 0;
   const int* flag = reinterpret_cast<const int*>(p->view_flag.p);
-  hipLaunchKernelGGL(rtd_view_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, (const double*)p->view_l + c0 * ls, ls,
+  hipLaunchKernelGGL(rtd_view_apply_kernel, grid_1d(total), dim3(256), 0, p->stream, (const double*)p->view_l + c0 * ls, ls,
                      flag + c0 * fs, fs, X, (int)N, (int)nmu, (long)E, (long)cnt, out + c0 * nmu * E);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("rtd_view_apply_kernel: ") + hipGetErrorString(e));
@@ -2720,7 +2759,7 @@ static int view_queued(rtd_plan* p, bool want_u, bool want_u0) {
 // what rtd_plan_fetch_view and rtd_plan_fetch_band_view refuse alike
 static int view_refused(rtd_plan* p, const double* u_mu) {
   if (p->view_nmu <= 0) return fail(RTD_ERR_STATE, "set_view_mu must precede fetch_view");
-  if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "nothing to fetch");
+  if (!has_results(p, true)) return fail(RTD_ERR_STATE, "nothing to fetch");
   if (u_mu && !p->res_has_u) return fail(RTD_ERR_STATE, "fetch_view: the latest evaluation formed no u (no azimuths, or u was not wanted)");
   if (u_mu && p->view_nt_mode == 1 && p->res_nt && !p->view_u_resident)
     return fail(RTD_ERR_STATE, "fetch_view: with the corrections at the angles (set_view_nt) the view of u is formed by the evaluation, and the "
@@ -2728,28 +2767,12 @@ static int view_refused(rtd_plan* p, const double* u_mu) {
   return 0;
 }
 
-static int view_fetch_queued(rtd_plan* p, double* u_mu, double* u0_mu) {
+static int view_fetch_queued(rtd_plan* p, double* u_mu, double* u0_mu, const char* band_label = nullptr) {
   int rc = view_queued(p, u_mu != nullptr, u0_mu != nullptr);
   if (rc) return rc;
-  const ResultShape r(p);
-  const int64_t nmu = p->view_nmu;
-  if (u_mu) HIP_TRY(hipMemcpyAsync(u_mu, p->ev_view_u, (size_t)(r.C * nmu * r.nt * r.np) * 8, hipMemcpyDeviceToHost, p->stream));
-  if (u0_mu) HIP_TRY(hipMemcpyAsync(u0_mu, p->ev_view_u0, (size_t)(r.C * nmu * r.nt) * 8, hipMemcpyDeviceToHost, p->stream));
-  return check_status(p, u_mu != nullptr);  // (u0 comes from Fourier mode 0 alone)
-}
-
-static int band_view_fetch_queued(rtd_plan* p, double* u_mu, double* u0_mu) {
-  int rc = view_queued(p, u_mu != nullptr, u0_mu != nullptr);
-  if (rc) return rc;
-  const ResultShape r(p);
-  const int64_t PK = (int64_t)(r.C / p->band_G) * p->band_K, Eu = p->view_nmu * r.nt * r.np, Eu0 = p->view_nmu * r.nt;
-  if (u_mu && (rc = grow(p, p->rb_view_u, PK * Eu))) return rc;
-  if (u0_mu && (rc = grow(p, p->rb_view_u0, PK * Eu0))) return rc;
-  hipError_t e = hipSuccess;
-  if (u_mu) e = band_reduce(p, p->ev_view_u, 0xFFFF, Eu, p->rb_view_u, u_mu);
-  if (e == hipSuccess && u0_mu) e = band_reduce(p, p->ev_view_u0, 0xFF, Eu0, p->rb_view_u0, u0_mu);
-  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("fetch_band_view: ") + hipGetErrorString(e));
-  return check_status(p, u_mu != nullptr);
+  Products xs;
+  view_products(p, u_mu, u0_mu, &xs);
+  return deliver(p, xs, band_label);
 }
 
 int rtd_plan_fetch_view(rtd_plan* p, double* u_mu, double* u0_mu) {
@@ -2765,15 +2788,10 @@ int rtd_plan_fetch_band_view(rtd_plan* p, double* u_mu, double* u0_mu) {
   int rc = view_refused(p, u_mu);
   if (rc) return rc;
   if (!view_band_consistent(p)) return fail(RTD_ERR_ARG, "fetch_band_view: the columns of a band profile must carry identical angles");
-  return drained(p, band_view_fetch_queued(p, u_mu, u0_mu));
+  return drained(p, view_fetch_queued(p, u_mu, u0_mu, "fetch_band_view"));
 }
 
 // ---- Lambertian albedo sweeps (rtd_plan_couple_lambert, rtd_plan_couple_lambert_band; kernels rtd_lambert.hip) ------------------------
-// The scratch budget of the coupled arrays in doubles (RTD_LAMBERT_BYTES, default 256 MiB; not a tuned number).
-static int64_t lambert_budget() {
-  const char* env = getenv("RTD_LAMBERT_BYTES");
-  return std::max<long long>(env ? atoll(env) : (256ll << 20), 8) / 8;
-}
 
 // what the two entry points and the plan-free rtd_lambert_kappa refuse of the caller's arrays: rows_ok lists the admissible albedo_rows
 static int lambert_args_refused(int64_t C, int32_t nalb, const double* albedo, int64_t rows, const int64_t* rows_ok, int nrows_ok,
@@ -2792,8 +2810,6 @@ static int lambert_args_refused(int64_t C, int32_t nalb, const double* albedo, i
   return 0;
 }
 
-static bool lambert_sharded(const rtd_plan* p) { return p->comm || p->d.m0 != 0 || p->d.mstep != 1 || p->d.mtot != p->d.M; }
-
 // the RTD_ERR_STATE cases of the two entry points
 static int lambert_state_refused(rtd_plan* a, rtd_plan* b, bool want_u, const double* u_mu, const double* u0_mu) {
   if (a->d.C != b->d.C || a->d.L != b->d.L || a->d.N != b->d.N || a->device != b->device)
@@ -2801,9 +2817,9 @@ static int lambert_state_refused(rtd_plan* a, rtd_plan* b, bool want_u, const do
   if (b->d.M != 1 || b->d.beam || b->d.Ns != 0 || b->d.NBDRF != 0)
     return fail(RTD_ERR_STATE, "couple_lambert: the companion must have one Fourier mode, no beam, no isotropic source and no BDRF");
   if (a->d.NBDRF != 0) return fail(RTD_ERR_STATE, "couple_lambert: the primary must be solved over a black surface (nbdrf = 0)");
-  if (lambert_sharded(a) || lambert_sharded(b)) return fail(RTD_ERR_STATE, "couple_lambert is not combined with a mode shard or a communicator");
+  if (sharded(a) || sharded(b)) return fail(RTD_ERR_STATE, "couple_lambert is not combined with a mode shard or a communicator");
   for (const rtd_plan* p : {a, b})
-    if (p->ev_ntau < 1 || !p->solved || p->res_order == rtd_plan::RES_NONE) return fail(RTD_ERR_STATE, "couple_lambert: nothing to couple (a plan holds no evaluated results)");
+    if (!has_results(p, true)) return fail(RTD_ERR_STATE, "couple_lambert: nothing to couple (a plan holds no evaluated results)");
   if (a->ev_ntau != b->ev_ntau || a->res_order != b->res_order)
     return fail(RTD_ERR_STATE, "couple_lambert: the two plans were evaluated at different numbers of points or in different tau-orders");
   if (want_u && !a->res_has_u) return fail(RTD_ERR_STATE, "couple_lambert: the primary's latest evaluation formed no u (no azimuths, or u was not wanted)");
@@ -2828,28 +2844,22 @@ static int lambert_queued(rtd_plan* a, rtd_plan* b, int32_t nalb, const double* 
   }
   HIP_TRY(hipStreamSynchronize(b->stream));  // (the companion's evaluation and view must have landed before the primary's stream reads them)
   b->stream_drained();
-  const ResultShape r(a);
-  const int64_t C = r.C, nt = r.nt, np = r.np, nmu = a->view_nmu;
-  const int64_t G = band ? a->band_G : 1, K = band ? a->band_K : 0, NA = nalb;
-  struct Item { double* host; const double *X, *Y; int64_t E; int nrep, mask, band_mask; } items[6];
-  int nitems = 0;
-  if (u) items[nitems++] = {u, a->ev_u, b->ev_u0, r.per_column_u(), (int)np, 7, 0xFFFF};
-  if (u0) items[nitems++] = {u0, a->ev_u0, b->ev_u0, r.per_column_u0(), 1, 3, 0xFF};
-  if (fup) items[nitems++] = {fup, a->ev_fl + r.flux_at(0), b->ev_fl + r.flux_at(0), nt, 1, 3, 0xFF};
-  if (fdn) items[nitems++] = {fdn, a->ev_fl + r.flux_at(1), b->ev_fl + r.flux_at(1), nt, 1, 3, 0xFF};
-  if (u_mu) items[nitems++] = {u_mu, a->ev_view_u, b->ev_view_u0, nmu * nt * np, (int)np, 7, 0xFFFF};
-  if (u0_mu) items[nitems++] = {u0_mu, a->ev_view_u0, b->ev_view_u0, nmu * nt, 1, 3, 0xFF};
-  // columns per chunk of an item: as many as fit the budget, one column (a band: one profile) at least
-  const int64_t budget = lambert_budget();
-  auto chunk_of = [&](const Item& it) { return G * std::min<int64_t>(C / G, std::max<int64_t>(1, budget / ((G + K) * NA * it.E))); };
+  const int64_t C = a->d.C, G = band ? a->band_G : 1, K = band ? a->band_K : 0, NA = nalb;
+  // the primary's outputs X and, entry for entry, the companion's mode-0 terms Y: E doubles per column of X, E / nrep of Y
+  Products xs, ys;
+  result_products(a, u, u0, fup, fdn, nullptr, &xs);
+  result_products(b, u, u0, fup, fdn, nullptr, &ys, true);
+  view_products(a, u_mu, u0_mu, &xs);
+  view_products(b, u_mu, u0_mu, &ys, true);
+  // columns per chunk of an output: as many as fit the budget, one column (a band: one profile) at least
+  const int64_t budget = budget_doubles(getenv("RTD_LAMBERT_BYTES"));
+  auto chunk_of = [&](const Product& x) { return G * columns_per_chunk(budget, (G + K) * NA * x.per, C / G); };
   int64_t work = 0;
-  for (int i = 0; i < nitems; ++i) work = std::max(work, chunk_of(items[i]) / G * (G + K) * NA * items[i].E);
+  for (int i = 0; i < xs.n; ++i) work = std::max(work, chunk_of(xs.v[i]) / G * (G + K) * NA * xs.v[i].per);
   const int64_t n_alb = rows * NA, n_small = n_alb + 3 * C + C * NA + (C + 1) / 2 + 1;
-  void* blk_v = nullptr;
-  size_t got = 0;
-  HIP_TRY(pooled_malloc(&blk_v, (size_t)(n_small + work) * 8, a->device, &got));
-  double* blk = static_cast<double*>(blk_v);
-  double *d_alb = blk, *d_f = d_alb + n_alb, *d_s = d_f + C, *d_e = d_s + C, *d_k = d_e + C, *d_work = blk + n_small;
+  Scratch blk;
+  HIP_TRY(blk.get(n_small + work, a->device));
+  double *d_alb = blk.data(), *d_f = d_alb + n_alb, *d_s = d_f + C, *d_e = d_s + C, *d_k = d_e + C, *d_work = d_alb + n_small;
   int* d_flag = reinterpret_cast<int*>(d_k + C * NA);
   hipStream_t st = a->stream;
   (void)hipGetLastError();
@@ -2862,34 +2872,30 @@ static int lambert_queued(rtd_plan* a, rtd_plan* b, int32_t nalb, const double* 
                              d_flag, st);
     e = hipGetLastError();
   }
-  for (int i = 0; i < nitems && e == hipSuccess; ++i) {
-    const Item& it = items[i];
-    const int64_t per = NA * it.E, chunk = chunk_of(it);
+  for (int i = 0; i < xs.n && e == hipSuccess; ++i) {
+    const Product &x = xs.v[i], &y = ys.v[i];
+    const bool every_mode = x.mask == 0xFFFF;  // u and its view: every azimuth of X takes the same element of Y, and Y's bits 0 ... 2 spoil
+    const int64_t E = x.per, per = NA * E, chunk = chunk_of(x);
     for (int64_t c0 = 0; c0 < C && e == hipSuccess; c0 += chunk) {
       const int64_t cnt = std::min(chunk, C - c0);
-      rtd_launch_lambert_couple(it.X + c0 * it.E, it.Y + c0 * (it.E / it.nrep), d_k + c0 * NA, d_flag + c0, it.mask, (long)cnt, nalb, (long)it.E,
-                                it.nrep, d_work, st);
+      rtd_launch_lambert_couple(x.dev + c0 * E, y.dev + c0 * y.per, d_k + c0 * NA, d_flag + c0, every_mode ? 7 : 3, (long)cnt, nalb, (long)E,
+                                (int)(E / y.per), d_work, st);
       e = hipGetLastError();
       if (e != hipSuccess) break;
       if (!band) {
-        e = hipMemcpyAsync(it.host + c0 * per, d_work, (size_t)(cnt * per) * 8, hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(x.host + c0 * per, d_work, (size_t)(cnt * per) * 8, hipMemcpyDeviceToHost, st);
       } else {  // the chunk's profiles reduced over g behind the coupled arrays, with the primary's weights
         const int64_t P = cnt / G;
         double* red = d_work + cnt * per;
-        hipLaunchKernelGGL(rtd_band_reduce_kernel, dim3((unsigned)((P * per + 255) / 256)), dim3(256), 0, st, (const double*)d_work,
-                           (const double*)a->band_w, (const int*)a->d.col_status + c0, it.band_mask, (long)P, (int)G, (int)K, (long)per, red);
+        hipLaunchKernelGGL(rtd_band_reduce_kernel, grid_1d(P * per), dim3(256), 0, st, (const double*)d_work,
+                           (const double*)a->band_w, (const int*)a->d.col_status + c0, x.mask, (long)P, (int)G, (int)K, (long)per, red);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(it.host + (c0 / G) * K * per, red, (size_t)(P * K * per) * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(x.host + (c0 / G) * K * per, red, (size_t)(P * K * per) * 8, hipMemcpyDeviceToHost, st);
       }
     }
   }
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(st);
-    pooled_free(blk, got, a->device);
-    return fail(RTD_ERR_HIP, std::string("couple_lambert: ") + hipGetErrorString(e));
-  }
-  rc = check_status(a, u != nullptr || u_mu != nullptr);  // (drains the primary's stream: the block is free behind it)
-  pooled_free(blk, got, a->device);
+  if (e != hipSuccess) return finish(e, st, "couple_lambert");
+  rc = check_status(a, xs.all_modes);  // (drains the primary's stream: the block is free behind it)
   const std::string keep = g_err;
   const int rc_b = check_status(b, false);
   if (rc) g_err = keep;
@@ -2931,16 +2937,11 @@ int rtd_lambert_kappa(int32_t device, int64_t ncols, int32_t nalb, const double*
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   const int64_t C = ncols, NA = nalb, n_alb = (int64_t)albedo_rows * NA, total = n_alb + 3 * C + C * NA + (C + 1) / 2 + 1;
-  void* blk_v = nullptr;
-  size_t got = 0;
-  HIP_TRY(pooled_malloc(&blk_v, (size_t)total * 8, device, &got));
-  double* blk = static_cast<double*>(blk_v);
-  double *d_alb = blk, *d_f = d_alb + n_alb, *d_s = d_f + C, *d_e = d_s + C, *d_k = d_e + C;
+  Scratch blk;
+  HIP_TRY(blk.get(total, device));
+  double *d_alb = blk.data(), *d_f = d_alb + n_alb, *d_s = d_f + C, *d_e = d_s + C, *d_k = d_e + C;
   int* d_flag = reinterpret_cast<int*>(d_k + C * NA);
-  hipError_t e = hipMemcpy(d_alb, albedo, (size_t)n_alb * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_f, fdown_bottom, (size_t)C * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_s, sph_albedo, (size_t)C * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && emission) e = hipMemcpy(d_e, emission, (size_t)C * 8, hipMemcpyHostToDevice);
+  hipError_t e = upload_parts(d_alb, {{albedo, n_alb}, {fdown_bottom, C}, {sph_albedo, C}, {emission, C}});
   if (e == hipSuccess) {
     (void)hipGetLastError();
     rtd_launch_lambert_kappa(d_alb, (long)(C / albedo_rows), nalb, d_f, d_s, emission ? d_e : nullptr, nullptr, nullptr, (long)C, d_k, d_flag,
@@ -2948,11 +2949,8 @@ int rtd_lambert_kappa(int32_t device, int64_t ncols, int32_t nalb, const double*
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(kappa, d_k, (size_t)(C * NA) * 8, hipMemcpyDeviceToHost);  // (waits for the kernel)
-  else (void)hipStreamSynchronize((hipStream_t)0);
   if (e == hipSuccess && flag) e = hipMemcpy(flag, d_flag, (size_t)C * 4, hipMemcpyDeviceToHost);
-  pooled_free(blk, got, device);
-  if (e != hipSuccess) return fail(RTD_ERR_HIP, std::string("lambert_kappa: ") + hipGetErrorString(e));
-  return 0;
+  return finish(e, (hipStream_t)0, "lambert_kappa");
 }
 
 int rtd_plan_set_nt(rtd_plan* p, int32_t nleg_all, const double* weighted_leg_all, const double* f_arr,
