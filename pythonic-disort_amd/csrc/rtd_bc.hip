@@ -47,7 +47,7 @@ namespace {
 // Against that two-kernel path this removes the Wp/Wq round trip through HBM (about 40 % of the stage's traffic).
 // ------------------------------------------------------------------------------------------------
 #ifndef RTD_BCF_WIN
-#define RTD_BCF_WIN 20  // layers of small vectors resident in LDS (12.6 KB per wavefront with the save area: 12 per CU)
+#define RTD_BCF_WIN 20  // layers of small vectors resident in LDS (9 792 B per wavefront with the save area: 16 per CU)
 #endif
 
 // Speculative, branch-free form of the same elimination with the diagonal as pivot at every step: straight-line
@@ -739,17 +739,21 @@ __global__ __launch_bounds__(64, 4) void rtd_bc_mfma_kernel(RtdDev d) {
     asm volatile("" : "+v"(lv));
     BwSet s;
     const LaneOff lo = lane_offsets(lv);
-    s.a = load_d_u(Am + (long)l * NN, lo.lane8);
-    s.y = load_d_u(Ym + (long)l * NN, lo.lane8);
+    // Streamed (non-temporal): the last use of every line.  Measured +1.4 % on the headline; the same policy on the FORWARD sweep's
+    // loads and stores lost 1 ... 4 % (they are what these loads find in the Infinity Cache).  profiles/bc_cache_policy/;
+    // HISTORY.md: "Cache policy of the 32-stream hand-off".
+    constexpr Mem P = Mem::STREAM;
+    s.a = load_d_u<P>(Am + (long)l * NN, lo.lane8);
+    s.y = load_d_u<P>(Ym + (long)l * NN, lo.lane8);
     long wso = 8 * ((long)l * Ws<NP>::SLOT + Ws<NP>::S);  // (opaque: see the forward loop's stores)
     asm("" : "+s"(wso));
     const double* wS = reinterpret_cast<const double*>(reinterpret_cast<const char*>(wsb) + wso);
-    s.h = load_d_u(wS, lo.lane8);
-    s.sl = ldg_u(wS, lo.col8, 8 * (Ws<NP>::SV - Ws<NP>::S));
-    s.rb = ldg_u(wS, lo.col8, 8 * (Ws<NP>::RB - Ws<NP>::S));
-    s.k = ldg_u(kk + l * NP, lo.col8);
+    s.h = load_d_u<P>(wS, lo.lane8);
+    s.sl = ldg_u<P>(wS, lo.col8, 8 * (Ws<NP>::SV - Ws<NP>::S));
+    s.rb = ldg_u<P>(wS, lo.col8, 8 * (Ws<NP>::RB - Ws<NP>::S));
+    s.k = ldg_u<P>(kk + l * NP, lo.col8);
     s.e = 0.0;
-    s.e = ldg_u(Ek + l * NP, lo.col8);
+    s.e = ldg_u<P>(Ek + l * NP, lo.col8);
     return s;
   };
   v4f64 w1, w2;

@@ -83,26 +83,38 @@ __device__ __forceinline__ unsigned block_local(unsigned v) {
   asm("" : "+v"(v));
   return v;
 }
+// Cache policy of an access, a compile-time argument because it is a bit of the instruction's encoding: KEEP is the plain access,
+// STREAM the non-temporal one (`nt`) for data that is not touched again: rtd_bc_mfma_kernel's backward operand loads.  The
+// address form is the same in both (global_load_dwordx2 v, v_off, s[b:b+1] offset:imm nt).
+enum class Mem { KEEP, STREAM };
+template <Mem P = Mem::KEEP>
 __device__ __forceinline__ double ldg_u(const double* ub, const unsigned off, const long cbytes = 0) {
-  return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(ub) + cbytes + (size_t)off);
+  const double* p = reinterpret_cast<const double*>(reinterpret_cast<const char*>(ub) + cbytes + (size_t)off);
+  if constexpr (P == Mem::STREAM) return __builtin_nontemporal_load(p);
+  else return *p;
 }
+template <Mem P = Mem::KEEP>
 __device__ __forceinline__ void stg_u(double* ub, const unsigned off, const long cbytes, const double v) {
-  *reinterpret_cast<double*>(reinterpret_cast<char*>(ub) + cbytes + (size_t)off) = v;
+  double* p = reinterpret_cast<double*>(reinterpret_cast<char*>(ub) + cbytes + (size_t)off);
+  if constexpr (P == Mem::STREAM) __builtin_nontemporal_store(v, p);
+  else *p = v;
 }
+template <Mem P = Mem::KEEP>
 __device__ __forceinline__ v4f64 load_d_u(const double* ub, const unsigned lane8) {  // row-major 16 x 16 matrix -> D layout
   v4f64 x;
-  x[0] = ldg_u(ub, lane8, 0);
-  x[1] = ldg_u(ub, lane8, 512);
-  x[2] = ldg_u(ub, lane8, 1024);
-  x[3] = ldg_u(ub, lane8, 1536);
+  x[0] = ldg_u<P>(ub, lane8, 0);
+  x[1] = ldg_u<P>(ub, lane8, 512);
+  x[2] = ldg_u<P>(ub, lane8, 1024);
+  x[3] = ldg_u<P>(ub, lane8, 1536);
   return x;
 }
+template <Mem P = Mem::KEEP>
 __device__ __forceinline__ v4f64 load_row_u(const double* ub, const unsigned kq8) {  // a 16-vector in row form
   v4f64 x;
-  x[0] = ldg_u(ub, kq8, 0);
-  x[1] = ldg_u(ub, kq8, 32);
-  x[2] = ldg_u(ub, kq8, 64);
-  x[3] = ldg_u(ub, kq8, 96);
+  x[0] = ldg_u<P>(ub, kq8, 0);
+  x[1] = ldg_u<P>(ub, kq8, 32);
+  x[2] = ldg_u<P>(ub, kq8, 64);
+  x[3] = ldg_u<P>(ub, kq8, 96);
   return x;
 }
 

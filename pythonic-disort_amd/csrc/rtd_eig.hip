@@ -889,6 +889,16 @@ __host__ __device__ constexpr int tri(int r, int c) { return r * (r + 1) / 2 + c
 #define RTD_ESTAMP(k)
 #endif
 
+// The 16-lane kernel's stores of Y, A, k, E and B are read next by another kernel (rtd_bc_mfma_kernel), after a whole window's worth
+// of them has gone by: streamed (non-temporal), they do not displace what that kernel keeps in the cache for its backward sweep.
+// The NP = 16 instances only: a wavefront of theirs never reads its own stores back (the 64-stream kernel's thermal branch does).
+// profiles/bc_cache_policy/; HISTORY.md: "Cache policy of the 32-stream hand-off".
+template <bool NT>
+__device__ __forceinline__ void handoff_store(double* p, const double v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
 template <int NP, int JV>  // JV: 2 = default; 3 = the assembly of Pm, Qm on the matrix cores (RTD_EIG_MFMA, NP = 16)
 __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EIGEN32_WAVES : 1)) void rtd_eigen_kernel(RtdDev d) {
   constexpr int GPW = 64 / NP;
@@ -1357,10 +1367,10 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     if (valid) {
       double* Ym = d.Ym + base * NP * NP;
 #pragma unroll
-      for (int i = 0; i < NP; ++i) Ym[i * NP + je] = ya[i];
-      d.kk[base * NP + je] = kj;
+      for (int i = 0; i < NP; ++i) handoff_store<NP == 16>(Ym + i * NP + je, ya[i]);
+      handoff_store<NP == 16>(d.kk + base * NP + je, kj);
       if constexpr (NP != 32) ekj = exp(-kj * dts);
-      d.Ek[base * NP + je] = ekj;
+      handoff_store<NP == 16>(d.Ek + base * NP + je, ekj);
     }
   };
   // NP = 32: Y leaves behind the beam stage, in one run of stores.  This kernel reloads spilled registers in the beam stage: stored
@@ -1465,8 +1475,8 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
     bv_dn = 0.5 * (s_j - d_j);
     if constexpr (NP != 32) {
       if (valid) {
-        d.Bv[base * 2 * NP + j] = bv_up;
-        d.Bv[base * 2 * NP + NP + j] = bv_dn;
+        handoff_store<NP == 16>(d.Bv + base * 2 * NP + j, bv_up);
+        handoff_store<NP == 16>(d.Bv + base * 2 * NP + NP + j, bv_dn);
       }
     }
     // 1/mu0 on an eigenvalue: the reference's solve (:226-231) meets a singular matrix
@@ -1515,7 +1525,7 @@ __global__ __launch_bounds__(64, (NP <= 16 ? RTD_EIGEN_WAVES : NP == 32 ? RTD_EI
   if (valid) {
     double* Am = d.Am + base * NP * NP;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) Am[i * NP + je] = aa[i];
+    for (int i = 0; i < NP; ++i) handoff_store<NP == 16>(Am + i * NP + je, aa[i]);
     if constexpr (NP == 32) {
       if (d.beam) {
         d.Bv[base * 2 * NP + j] = bv_up;
